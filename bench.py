@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- GCRA decisions/s of the MI355X engine on BASELINE.json's workload.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload uniform|zipf]
+    python bench.py [--gpus N --steps K --warmup W] [--workload uniform|zipf] [--full] [--dump-outputs DIR]
+
+A plain N = 1 run does what the headline figure needs and nothing else: set-up, W warmup steps, K timed steps, the line.
+--full adds everything else this file measures or checks (the oracle replay behind `verified`, the per-kernel profile
+behind `roofline`, the secondary workloads, the CPU baseline); --dump-outputs DIR writes the decisions of the last
+timed batch to DIR/allowed.npy, so that two builds can be compared output for output (the request streams are seeded).
 
 One "step" = one batch of 1 Mi requests (u32 slots already resident in HBM)
 decided and applied against a 10 M-key resident store through the C ABI
@@ -21,9 +26,10 @@ exchange the path has: aggregate metrics).  The line carries `per_gpu` (requests
 owned, allowed share, decisions/s): under Zipf the owner of the hottest key gets
 11.6 % of ALL traffic on top of its share.
 
-Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB: headline, roofline of the critical-path
-kernel, cpu_baseline, one number per secondary workload); everything else (per-stage tables, PMC provenance, notes)
-goes to gpurun_out/bench_detail.json.
+Output (rank 0): the LAST stdout line is ONE compact JSON object (< 4 KB: the headline; with --full also the roofline
+of the critical-path kernel, cpu_baseline, `verified` and one number per secondary workload -- a plain run says
+`"verified": null, "cpu_baseline": null` and carries no roofline); everything else (per-stage tables, PMC provenance,
+notes: next to nothing without --full) goes to the detail file, DETAIL_PATH below the tree.
 """
 import argparse
 import json
@@ -112,8 +118,17 @@ def parse():
                          "launches the N ranks itself (torch.distributed.run on 127.0.0.1) and fails if the node has fewer GPUs; under "
                          "torchrun it must agree with WORLD_SIZE.  Default: WORLD_SIZE, else 1")
     ap.add_argument("--plan-only", action="store_true", help="print what --gpus N would launch, as JSON, and exit (no GPU touched)")
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed steps of the headline run (ms_per_step = their time / this)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: besides the headline run, everything else this file measures or checks -- the oracle replay of the timed "
+                         "batches (`verified`), four more timed regions, the per-kernel profile and roofline, the secondary workloads "
+                         "(other stream / layout, general batches, per-key plans, output forms, string keys, the reference-shaped call) "
+                         "and the CPU baseline.  Without it: set-up, warmup, the timed steps, --dump-outputs, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last timed step handed its caller -- the decision of every request "
+                         "of that batch -- to DIR/allowed.npy (float32).  Same arguments, same inputs: two builds can be compared "
+                         "output for output")
     ap.add_argument("--workload", default="uniform", choices=["uniform", "zipf", "general", "general_zipf"],
                     help="uniform / zipf: one timestamp per batch (BASELINE configs[1] / [2]); general / general_zipf: the same "
                          "slot streams with a timestamp PER REQUEST, as every transport stamps them "
@@ -265,6 +280,21 @@ def run_gpu(eng, d_batches, out, now0, steps, warmup, dist, cnt_view, gathered, 
     return dt, it
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array} -> path/<name>.npy, float32.  What does not fit into an equal share of DUMP_LIMIT_BYTES
+    is cut to a fixed sample (seeded: the same elements in every run)."""
+    os.makedirs(path, exist_ok=True)
+    room = (DUMP_LIMIT_BYTES // len(arrays) - 4096) // 4   # elements per file (4096: more than a .npy header takes)
+    for name, arr in arrays.items():
+        arr = np.asarray(arr).reshape(-1)
+        if arr.size > room:
+            arr = arr[np.sort(np.random.default_rng(0).choice(arr.size, room, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float32))
+
+
 def stage_profile(eng, d_batches, out, now0, steps, it0, piped=True, nows=None):
     """`steps` more batches with a HIP event pair around each of the engine's kernels (recorded on the stream the
     kernel runs on).  piped=True: issued exactly like the timed region (the grouping of later batches overlaps
@@ -321,10 +351,11 @@ def roofline_entry(kernel, avg_ms, alg, ms_per_step, traffic, source):
     return r
 
 
-def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, general=False, profile=True, plans=None):
-    """One engine, one request stream: warmup + timed region (pipelined), the oracle replay of exactly those batches, then
-    the per-kernel profile.  general: every request carries its own timestamp (k_eval_general instead of k_eval_sorted).
-    plans: None / "one" = one registered plan for the table; "tiers4" / "tiers1000" = a plan per key (plan_tiers)."""
+def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, general=False, profile=True, plans=None, dump_dir=None):
+    """One engine, one request stream: warmup + timed region (pipelined) and, with --full, the oracle replay of exactly those
+    batches, then the per-kernel profile.  general: every request carries its own timestamp (k_eval_general instead of
+    k_eval_sorted).  plans: None / "one" = one registered plan for the table; "tiers4" / "tiers1000" = a plan per key
+    (plan_tiers).  dump_dir: --dump-outputs (the decisions of the last timed batch)."""
     import torch
     plans = a.plans if plans is None else plans
     eng = t.Engine(a.keys, a.batch, device=local, fixed_params=(a.layout == "fixed"))
@@ -343,6 +374,8 @@ def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, g
         cnt_view = device_counter_view(eng)
         gathered = torch.zeros(world * cnt_view.numel(), dtype=torch.int64, device=dev)
     dt, it = run_gpu(eng, d_batches, out, W.T0_NS, a.steps, a.warmup, dist, cnt_view, gathered, piped=not a.in_order, nows=nows)
+    if dump_dir:   # (batch it - 1 was the last timed one; its result set is whole until the ring comes round again)
+        dump_outputs(dump_dir, {"allowed": out[(it - 1) % OUT_RING].allowed[:a.batch].cpu().numpy()})
     c = eng.counters()
     engine_info = eng.info()   # (did the pipelined batches really overlap -- side streams kept, probe verdicts, grouping path)
     ms = 1e3 * dt / a.steps
@@ -353,7 +386,7 @@ def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, g
            "grouping_path": engine_info.get("grouping_path")}
     if plans not in (None, "one"):
         res["plans"] = plans
-    if rank == 0 and dist is None and seed_shift == 0 and not a.no_verify and not a.profile_run and not a.in_order and nb <= 400:
+    if a.full and rank == 0 and dist is None and seed_shift == 0 and not a.no_verify and not a.profile_run and not a.in_order and nb <= 400:
         # what the timed run left behind, taken before anything else touches the engine: counters, the result arrays of the
         # last batches, the state of every key -- compared with the oracle's replay of the same nb batches
         snap = {"batches": nb, "counters": c, "selfcheck": eng.selfcheck(), "state": eng.read_state(0, a.keys),
@@ -364,7 +397,7 @@ def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, g
             res["verified"] = {"ok": False, "error": f"{type(ex).__name__}: {ex}"[:160]}
         del snap
         log(f"  verified: {res['verified']}")
-    if rank == 0 and dist is None and seed_shift == 0 and not a.profile_run and not a.in_order and os.environ.get("TC_BENCH_REPEATS", "1") != "0":
+    if a.full and rank == 0 and dist is None and seed_shift == 0 and not a.profile_run and not a.in_order and os.environ.get("TC_BENCH_REPEATS", "1") != "0":
         # the timed region is 20 x 44 us = 0.9 ms -- four more regions of the same length right behind it (the
         # stream goes on), so that a 3 % difference between two rounds can be told from noise.  `value` is the FIRST region's.
         reps = [ms]
@@ -373,7 +406,7 @@ def measure_stream(a, t, W, stream, dev, local, rank, seed_shift, dist, world, g
             reps.append(1e3 * dt_r / a.steps)
         res["repeats"] = {"ms_per_step": reps, "median": float(np.median(reps)), "min": min(reps), "max": max(reps)}
         log("  five regions, ms per step: " + " ".join(f"{x:.4f}" for x in reps))
-    if rank == 0 and profile and not a.profile_run:
+    if a.full and rank == 0 and profile and not a.profile_run:
         piped = stage_profile(eng, d_batches, out, W.T0_NS, a.steps, it, piped=True, nows=nows)
         inorder = stage_profile(eng, d_batches, out, W.T0_NS, a.steps, it + a.steps, piped=False, nows=nows)
         tag = ("general_" if general else "") + stream
@@ -1123,6 +1156,26 @@ def launch_plan(a, argv, env):
     return "launch", cmd
 
 
+def run_child(cmd):
+    """The launcher of the N ranks as a child (not an exec: counting the devices may have opened the GPU, and a process that
+    holds it keeps its program) -> its exit status.  SIGTERM / SIGINT sent to this process alone go on to the child, and the
+    child does not outlive this process's wait."""
+    import signal
+    import subprocess
+    started = []   # (the handlers stand before the child exists: no signal falls between the two)
+    old = {s: signal.signal(s, lambda signum, frame: [c.send_signal(signum) for c in started]) for s in (signal.SIGTERM, signal.SIGINT)}
+    try:
+        started.append(subprocess.Popen(cmd))
+        rc = started[0].wait()
+        return rc if rc >= 0 else 128 - rc   # (ended by signal n: 128 + n, as a shell reports it)
+    finally:
+        if started and started[0].poll() is None:
+            started[0].terminate()
+            started[0].wait()
+        for s, h in old.items():
+            signal.signal(s, h)
+
+
 def main():
     a = parse()
     kind, plan = launch_plan(a, sys.argv[1:], os.environ)
@@ -1131,6 +1184,8 @@ def main():
         return
     if kind == "error":
         sys.exit(f"bench.py: {plan}")
+    if a.dump_outputs and (kind == "launch" or plan > 1 or os.environ.get("TC_BENCH_FORCE_DIST") == "1"):
+        sys.exit("bench.py: --dump-outputs writes the decisions of the N = 1 run; with several ranks nothing would be written")
     if kind == "launch":
         if os.environ.get("TC_BENCH_ONE_DEVICE") != "1":  # (that switch puts every rank on GPU 0, over gloo: what a 1-GPU box can test)
             import torch
@@ -1139,7 +1194,7 @@ def main():
                 sys.exit(f"bench.py: --gpus {a.gpus} but this node shows {have} GPU(s); nothing was measured")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush()
-        os.execv(plan[0], plan)  # the ranks' rank 0 prints the line
+        sys.exit(run_child(plan))  # the ranks' rank 0 prints the line
     import torch
 
     import throttlecrab_amd as t
@@ -1234,7 +1289,7 @@ def main():
     general = a.workload.startswith("general")
     stream = {"general": "uniform", "general_zipf": "zipf"}.get(a.workload, a.workload)
     log(f"headline: {a.workload} / {a.layout}")
-    main_res, eng, d_batches, dt = measure_stream(a, t, W, stream, dev, local, rank, 0, None, 1, general=general)
+    main_res, eng, d_batches, dt = measure_stream(a, t, W, stream, dev, local, rank, 0, None, 1, general=general, dump_dir=a.dump_outputs)
     cfg_no = {"uniform": 1, "zipf": 2}[stream]
     result = {
         "metric": "GCRA decisions/sec, 10M keys", "value": main_res["value"], "unit": "decisions/s",
@@ -1284,7 +1339,7 @@ def main():
                 errors[name] = f"{type(ex).__name__}: {ex}"[:200]
                 print(f"[bench] secondary leg '{name}' failed: {errors[name]}", file=sys.stderr, flush=True)
 
-        if not a.no_also and not a.profile_run:
+        if a.full and not a.no_also and not a.profile_run:
             other = "zipf" if stream == "uniform" else "uniform"
             held = {}
 
@@ -1362,7 +1417,7 @@ def main():
                 result["abi_shape"]["verified"] = ab["verified"]["ok"]
                 verified["abi_shape"] = ab["verified"]
             leg("abi shape (host pointers, string keys, per-request parameters)", abi_shape)
-        if not a.no_cpu and not a.profile_run:
+        if a.full and not a.no_cpu and not a.profile_run:
             def cpu():
                 result["cpu_baseline"] = cpu_baseline(stream, a.keys, a.batch, a.cpu_sample_batches)
             leg("cpu baseline", cpu)
@@ -1375,7 +1430,7 @@ def main():
             result["verified_legs"] = len(verified)                                        # how many legs were replayed
             result["verify_failed"] = sorted(k for k, v in verified.items() if not v.get("ok"))   # ... and which of them differ
         else:
-            result["verified"] = None   # (--no-verify / --profile-run: nothing was replayed)
+            result["verified"] = None   # (no --full, --no-verify or --profile-run: nothing was replayed)
         emit(result, detail)
     eng.close()
 

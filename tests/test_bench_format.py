@@ -158,6 +158,40 @@ def test_verify_run_accepts_the_oracle_and_rejects_a_flipped_decision():
     assert not bench.verify_run(dict(snap, counters=dict(snap["counters"], allowed=allowed - 1)), host, 0, per_slot, keys, batch, False)["ok"]
 
 
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per array; an array too large for its share of the limit is cut to the same
+    (seeded) sample in every run, so that two builds' files still compare element for element"""
+    import numpy as np
+    small = (np.arange(1000) % 2).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), {"allowed": small})
+    got = np.load(tmp_path / "a" / "allowed.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)
+    big = np.random.default_rng(1).integers(0, 2, 100_000).astype(np.uint8)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"allowed": big, "other": big[::-1]})
+    files = [tmp_path / d / f for d in ("b", "c") for f in ("allowed.npy", "other.npy")]
+    assert sum(os.path.getsize(f) for f in files[:2]) <= 1 << 16
+    b, c = np.load(files[0]), np.load(files[2])
+    assert b.dtype == np.float32 and 1000 < b.size < big.size and np.array_equal(b, c)
+    assert set(np.unique(b)) <= {0.0, 1.0} and not np.array_equal(b, np.load(files[1]))
+
+
+def test_the_launcher_child_hands_back_its_exit_status_and_gets_the_parents_signals():
+    """`--gpus N` started plainly runs the ranks' launcher as a child: bench.py exits with the child's status, and a
+    SIGTERM sent to bench.py alone reaches the child (which here answers it with exit status 7)."""
+    import signal
+    assert bench.run_child([sys.executable, "-c", "import sys; sys.exit(3)"]) == 3
+    assert bench.run_child([sys.executable, "-c", "pass"]) == 0
+    before = signal.getsignal(signal.SIGTERM)
+    child = ("import os, signal, sys\n"
+             "signal.signal(signal.SIGTERM, lambda n, f: sys.exit(7))\n"
+             "os.kill(os.getppid(), signal.SIGTERM)\n"      # the parent (this process, inside run_child) is signalled alone
+             "signal.pause()\n")
+    assert bench.run_child([sys.executable, "-c", child]) == 7
+    assert signal.getsignal(signal.SIGTERM) is before
+
+
 def test_gpus_flag_launches_the_ranks_itself():
     """`--gpus N` was parsed and ignored (ranks came from torchrun's environment only, so a plain
     `python bench.py --gpus 8` ran one rank and said n_gpus: 1).  Now: a plain start with N > 1 launches the N ranks

@@ -125,6 +125,14 @@ def _free_port():
     return p
 
 
+# Every other CU for the fillers.  The driver deals a queue's CU mask out to the chip's 8 XCCs bit by bit (bit i -> XCC i % 8,
+# CU i / 8 of that XCC), so a mask of every other BIT (0x55555555) names every CU of XCCs 0, 2, 4, 6 and none of the others -- a
+# queue that cannot run on half of the dies, which newer runtimes refuse (hipExtStreamCreateWithCUMask: "out of memory"; 0x33333333
+# likewise).  Every other BYTE is every other CU of every XCC; its bits also come in adjacent pairs, as hsa_amd_queue_cu_set_mask
+# (hsa_ext_amd.h) asks of chips that schedule CUs pairwise.
+EVERY_OTHER_CU = [0x00FF00FF] * 8
+
+
 def _contender(rank, seconds, q):
     sys.path.insert(0, ROOT)
     import torch
@@ -144,7 +152,7 @@ def _contender(rank, seconds, q):
     # fillers take wave slots, LDS and whole CUs away from the kernels that wait for other workgroups: half of the
     # CUs for 3 ms, every other CU, or every CU's LDS -- launched just before a batch, still resident while its kernels run
     fillers = os.environ.get("TC_STRESS_FILLERS", "1") == "1"
-    masks = [[0xFFFFFFFF] * 4 + [0] * 4, [0x55555555] * 8, None]
+    masks = [[0xFFFFFFFF] * 4 + [0] * 4, EVERY_OTHER_CU, None]
     while time.time() < t_end:
         kind = rounds % 4
         if fillers and rounds % 3 != 2:
@@ -202,7 +210,15 @@ def test_two_processes_contend_for_one_device():
     procs = [ctx.Process(target=_contender, args=(r, seconds, q)) for r in range(2)]
     for p in procs:
         p.start()
-    got = [q.get(timeout=seconds * 10 + 300) for _ in procs]
+    import queue
+    got, give_up = [], time.time() + seconds * 10 + 300
+    while len(got) < len(procs):
+        try:
+            got.append(q.get(timeout=1))
+        except queue.Empty:   # (a contender that died reports nothing: say so at once instead of waiting for the time limit)
+            died = [(r, p.exitcode) for r, p in enumerate(procs) if p.exitcode not in (None, 0)]
+            assert not died, f"contender (rank, exit code) {died} ended without a result"
+            assert time.time() < give_up, "no result from the contenders"
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
@@ -276,7 +292,7 @@ def test_waiting_kernels_make_progress_beside_fillers(filler):
     eng.register_params_uniform(200_000, 10**9, 1)
     tt = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).cuda()
     spec = {"half_the_cus": dict(blocks=2048, microseconds=4000, cu_mask=[0xFFFFFFFF] * 4 + [0] * 4),
-            "every_other_cu": dict(blocks=2048, microseconds=4000, cu_mask=[0x55555555] * 8),
+            "every_other_cu": dict(blocks=2048, microseconds=4000, cu_mask=EVERY_OTHER_CU),
             "all_lds": dict(blocks=256, microseconds=4000, lds_bytes=128 * 1024),
             "oversubscribed": dict(blocks=8192, microseconds=600)}[filler]
     host_counts = eng.host_alloc(3, np.uint32)

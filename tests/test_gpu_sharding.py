@@ -111,8 +111,37 @@ def test_bench_gpus_flag_launches_that_many_ranks(route):
     assert abs(sum(g["share_of_traffic"] for g in d["per_gpu"]) - 1.0) < 1e-6 and min(g["share_of_traffic"] for g in d["per_gpu"]) > 0.3
 
 
+def test_plain_bench_run_is_lean_and_dumps_the_last_timed_batch(tmp_path):
+    """Without --full: the contract keys, nothing replayed, no roofline, no CPU baseline, no secondary workload -- and
+    --dump-outputs writes the decisions of the LAST timed batch: the oracle's for batch warmup + steps - 1 of the same
+    seeded stream (Zipf over few keys: the hot keys run out of burst, so both decisions occur)."""
+    import bench
+    from oracle import oracle as O
+    from throttlecrab_amd import workload as W
+    keys, batch, steps, warmup = 200_000, 65536, 3, 2
+    d = _bench_line(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--keys", str(keys), "--batch", str(batch),
+                     "--workload", "zipf", "--dump-outputs", str(tmp_path)], {})
+    for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["ms_per_step"] > 0 and d["unit"] == "decisions/s" and d["dtype"] == "int64"
+    assert abs(d["value"] - batch / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]   # (both rounded to six digits)
+    assert d["verified"] is None and d["cpu_baseline"] is None and "roofline" not in d and "ms_per_step_median5" not in d
+    for k in ("uniform_stream", "wide_layout", "general_uniform", "general_zipf", "per_key_plans", "string_keys", "abi_shape", "errors"):
+        assert k not in d, k
+    assert sorted(os.listdir(tmp_path)) == ["allowed.npy"]
+    got = np.load(tmp_path / "allowed.npy")
+    assert got.dtype == np.float32 and got.shape == (batch,)
+    nb = steps + warmup
+    host = bench.make_batches("zipf", keys, batch, nb)
+    orc = O.DenseOracle(keys)
+    for i in range(nb):
+        ref = orc.batch_slots(host[i], *W.REF_PARAMS, 1, W.T0_NS + i * 1_000_000)
+    assert 0 < int(ref.allowed.sum()) < batch
+    assert np.array_equal(got, ref.allowed.astype(np.float32))
+
+
 def test_bench_gpus_1_prints_the_single_gpu_line():
-    d = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "2", "--no-cpu", "--no-also", "--keys", "200000", "--batch", "65536"], {})
+    d = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-cpu", "--no-also", "--keys", "200000", "--batch", "65536"], {})
     assert d["n_gpus"] == 1 and "per_gpu" not in d and d["config"]["batch"] == 65536 and d["verified"] is True
     for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k

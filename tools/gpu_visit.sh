@@ -11,8 +11,8 @@ for S in $STEPS; do
     tests) timeout 400 python -m pytest tests -m gpu -x -q --timeout 120 > $O/pytest_gpu.log 2>&1; echo "tests rc=$?"; tail -5 $O/pytest_gpu.log ;;
     quick) timeout 600 python -m pytest tests/test_gpu_prefill.py tests/test_gpu_fixed.py tests/test_gpu_slots.py -m gpu -x -q > $O/pytest_quick.log 2>&1; echo "quick rc=$?"; tail -15 $O/pytest_quick.log ;;
     general) timeout 600 python -m pytest tests/test_gpu_slots.py tests/test_gpu_fixed.py tests/test_gpu_fuzz.py tests/test_gpu_robustness.py -m gpu -x -q > $O/pytest_general.log 2>&1; echo "general tests rc=$?"; tail -4 $O/pytest_general.log
-             for WL in general general_zipf; do timeout 300 python bench.py --workload $WL --no-also --no-cpu --steps 40 --warmup 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['stream'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s', 'kernel', d.get('roofline',{}).get('avg_ms'))"; done ;;
-    generalq) for WL in general general_zipf; do timeout 300 python bench.py --workload $WL --no-also --no-cpu --steps 40 --warmup 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['stream'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s', 'kernel', d.get('roofline',{}).get('avg_ms'))"; done ;;
+             for WL in general general_zipf; do timeout 300 python bench.py --full --workload $WL --no-also --no-cpu --steps 40 --warmup 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['stream'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s', 'kernel', d.get('roofline',{}).get('avg_ms'))"; done ;;
+    generalq) for WL in general general_zipf; do timeout 300 python bench.py --full --workload $WL --no-also --no-cpu --steps 40 --warmup 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['stream'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s', 'kernel', d.get('roofline',{}).get('avg_ms'))"; done ;;
     dist) timeout 300 python -m pytest tests/test_gpu_route.py tests/test_gpu_sharding.py -m gpu -x -q > $O/pytest_route.log 2>&1; echo "route tests rc=$?"; tail -4 $O/pytest_route.log
           for RT in exchange replicate; do
             TC_BENCH_ONE_DEVICE=1 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 20 --warmup 5 --route $RT --workload zipf > $O/dist2_${RT}.txt 2> $O/dist2_${RT}.err; echo "2 ranks on one GPU, $RT zipf rc=$?"; tail -1 $O/dist2_${RT}.txt | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['route'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s  imbalance', d['imbalance_max_over_mean'], 'router ms', d.get('router_ms_per_step'))"; grep -i "falling back\|Traceback" $O/dist2_${RT}.err | head -3
@@ -36,7 +36,7 @@ for S in $STEPS; do
     keytests) timeout 600 python -m pytest tests/test_gpu_keys.py tests/test_gpu_keys_spec.py tests/test_gpu_metrics.py tests/test_gpu_snapshot.py -m gpu -x -q > $O/pytest_keys.log 2>&1; echo "key tests rc=$?"; tail -4 $O/pytest_keys.log ;;
     routeflaky) for i in $(seq 1 40); do timeout 120 python -m pytest tests/test_gpu_route.py -m gpu -x -q --timeout 60 > $O/rf_$i.log 2>&1; if grep -q failed $O/rf_$i.log; then echo "run $i FAILED"; grep -E "^E  |FAILED|assert" $O/rf_$i.log | head -12; else rm $O/rf_$i.log; fi; done; echo loop done ;;
     ab) timeout 600 python tools/ab_step.py 100 > $O/ab_step.txt 2>&1; echo "ab rc=$?"; cat $O/ab_step.txt ;;
-    bench) TC_BENCH_VERBOSE=1 timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
+    bench) TC_BENCH_VERBOSE=1 timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
            tail -c 4200 $O/bench_stdout.txt; echo; wc -c $O/bench_stdout.txt; cp gpurun_out/bench_detail.json $O/ 2>/dev/null ;;
     prof) bash tools/gpu_round.sh $TAG uniform_fixed zipf_fixed general_uniform_fixed general_zipf_fixed ;;
     timeline) cd /tmp; export TMPDIR=/tmp

@@ -12,7 +12,7 @@ for S in $STEPS; do
     tests) timeout 900 python -m pytest tests -m gpu -x -q --timeout 300 > $O/pytest_gpu.log 2>&1; echo "tests rc=$?"; tail -5 $O/pytest_gpu.log ;;
     timed) timeout 900 python -m pytest tests/test_gpu_timed_config.py -m gpu -x -q --timeout 300 --durations=5 > $O/pytest_timed.log 2>&1; echo "timed-config tests rc=$?"; tail -12 $O/pytest_timed.log ;;
     quick) timeout 600 python -m pytest tests/test_gpu_prefill.py tests/test_gpu_fixed.py tests/test_gpu_slots.py tests/test_gpu_bucket.py -m gpu -x -q > $O/pytest_quick.log 2>&1; echo "quick rc=$?"; tail -6 $O/pytest_quick.log ;;
-    bench) TC_BENCH_VERBOSE=1 timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
+    bench) TC_BENCH_VERBOSE=1 timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_stdout.txt 2> $O/bench_stderr.txt; echo "bench rc=$?"
            tail -c 4200 $O/bench_stdout.txt; echo; wc -c $O/bench_stdout.txt; cp gpurun_out/bench_detail.json $O/ 2>/dev/null; grep -i "verified\|failed" $O/bench_stderr.txt | head -20 ;;
     bench200) for WL in uniform zipf; do timeout 300 python bench.py --steps 200 --warmup 10 --no-also --no-cpu --no-verify --workload $WL 2>/dev/null | tail -1 > $O/bench200_$WL.json; summ "d['config']['stream'], round(d['ms_per_step']*1e3,1), 'us/step', round(d['value']/1e9,2), 'G/s'" < $O/bench200_$WL.json; done ;;
     perkey) bash tools/gpu_round.sh $TAG uniform_fixed_tiers1000 zipf_fixed_tiers1000 ;;
