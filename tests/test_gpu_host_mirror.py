@@ -83,6 +83,17 @@ def test_cpp_sweep_policy_program():
     assert "all tests passed" in out.stdout
 
 
+def test_cpp_hot_list_program():
+    """The hot list's maker (throttlecrab_amd/csrc/hot_list.hpp: one note per slot, the 512 longest runs, the keep-or-remake
+    rule) against a brute-force sort of the notes: no GPU needed."""
+    exe = os.path.join(ROOT, "tests", "cpp", "test_hot_list")
+    src = os.path.join(ROOT, "tests", "cpp", "test_hot_list.cpp")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I" + os.path.join(ROOT, "throttlecrab_amd", "csrc"), src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "all tests passed" in out.stdout
+
+
 def test_cpp_kernel_math_properties_on_host():
     """gcra_math.hpp compiled for the host: closed form == sequence, the host-side proof behind the
     direct-store evaluation, late readers harmless (tests/cpp/test_math_host.hip). No GPU needed."""

@@ -1,5 +1,6 @@
 // slots.hip -- tc_rate_limit_batch_slots: staging, grouping (radix sort / bucket path), evaluation, one-launch small batches
 #include "engine.hpp"
+#include "hot_list.hpp"
 #include <chrono>
 
 // ---- batch over slots -------------------------------------------------------
@@ -304,62 +305,17 @@ static bool outputs_back_in_one_launch(tc_engine* e, const tc_batch& b, hipStrea
     return ok;
 }
 
-// -> true: the list changed (h.made is the new one)
+// -> true: the list changed (h.made is the new one).  The selection itself -- one note per slot, the rp::HOT_MAX longest, the
+// keep-or-remake rule -- is plain C++ over plain arrays: hot_list.hpp (run without an engine by tests/cpp/test_hot_list.cpp)
 static bool hot_make(tc_engine::Hot& h, uint64_t capacity) {
-    // one note per slot (the longest run), through a scratch hash: 8 192 notes at most, no sort of them all (a first version
-    // sorted the notes twice and cost the pipeline 0.3 ms every 8th batch)
-    constexpr uint32_t SCR = 2u * ev::HEAVY_SLOTS;
-    if (h.scratch.size() != SCR) h.scratch.assign(SCR, 0ull);
-    else std::fill(h.scratch.begin(), h.scratch.end(), 0ull);
-    auto probe = [&](uint32_t slot) -> unsigned long long& { // entry: (slot + 1) << 32 | length
-        uint32_t at = (slot * 0x9E3779B1u) >> (32 - (ev::HEAVY_BITS + 2));
-        while (h.scratch[at] != 0ull && (uint32_t)(h.scratch[at] >> 32) != slot + 1u) at = (at + 1u) & (SCR - 1u);
-        return h.scratch[at];
-    };
-    std::vector<unsigned long long>& found = h.found; // length << 32 | ~slot: descending = longest first, then by slot
-    found.clear();
-    for (uint32_t i = 0; i < ev::HEAVY_SLOTS; ++i) {
-        const unsigned long long v = ((volatile unsigned long long*)h.notes_host)[i];
-        const uint32_t len = (uint32_t)(v >> 44), slot = (uint32_t)v;
-        if (len < h.heavy_min || slot >= capacity) continue;
-        unsigned long long& en = probe(slot);
-        if ((uint32_t)en < len) en = ((unsigned long long)(slot + 1u) << 32) | len;
-    }
-    for (const unsigned long long en : h.scratch)
-        if (en) found.push_back(((unsigned long long)(uint32_t)en << 32) | (0xFFFFFFFFu - ((uint32_t)(en >> 32) - 1u)));
-    if (found.size() > rp::HOT_MAX) {
-        std::nth_element(found.begin(), found.begin() + rp::HOT_MAX, found.end(), std::greater<unsigned long long>());
-        found.resize(rp::HOT_MAX);
-    }
-    std::sort(found.begin(), found.end(), std::greater<unsigned long long>());
-    std::vector<uint32_t> now(found.size());
-    for (size_t i = 0; i < found.size(); ++i) now[i] = 0xFFFFFFFFu - (uint32_t)found[i];
-    // Keep the installed tables while the list still serves: nine in ten of its slots are still noted (else it is stale: made
-    // afresh, so that the table does not fill with slots that stopped being hot), and no slot with a run long enough to endanger a
-    // range (a quarter of what a block finishes) is missing from it.  Which slots are hot is all that counts -- the rank form
-    // does not care about their order -- and the tail of a skewed stream's list changes with every look (slots around heavy_min
-    // requests per batch come and go; in round 6's first version so did the boundary between the 64th and the 65th heaviest,
-    // and every change cost six installs and the hints about the ranges).
-    bool same = !h.made.empty();
-    if (same) {
-        std::vector<uint32_t> cur(h.made);
-        std::sort(cur.begin(), cur.end());
-        for (size_t i = 0; i < found.size() && same; ++i) {
-            const uint32_t len = (uint32_t)(found[i] >> 32), sl = 0xFFFFFFFFu - (uint32_t)found[i];
-            if (len < rs::FIN_CAP / 4u) break; // (sorted by length, longest first)
-            same = std::binary_search(cur.begin(), cur.end(), sl);
-        }
-        size_t both = 0;
-        for (const uint32_t sl : h.made) both += probe(sl) != 0ull ? 1u : 0u; // (noted at all: on the new list or just below its cut)
-        same = same && both * 10u >= h.made.size() * 9u && now.size() * 4u <= h.made.size() * 5u + 128u; // (... nor has a crowd of new hot slots turned up)
-    }
-    if (now.empty() && h.made.empty()) same = true;
-    if (same) {
+    static_assert(hl::ENGINE.notes == ev::HEAVY_SLOTS && hl::ENGINE.scratch_bits == ev::HEAVY_BITS + 2u && hl::ENGINE.hot_max == rp::HOT_MAX &&
+                      hl::ENGINE.long_run == rs::FIN_CAP / 4u,
+                  "hot_list.hpp: the limits the list is made by are the kernels'");
+    if (!hl::make_list(h.notes_host, hl::ENGINE, h.heavy_min, capacity, h.scratch, h.found, h.made)) {
         h.stable_looks.fetch_add(1u, std::memory_order_relaxed);
         return false;
     }
     h.stable_looks.store(0u, std::memory_order_relaxed);
-    h.made.swap(now);
     h.lists_made++;
     return true;
 }
