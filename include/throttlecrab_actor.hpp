@@ -367,11 +367,20 @@ class BasicRateLimiterActor {
         }
     }
 
+    // A limiter that can answer a batch as ThrottleResponses itself (RateLimiter::submit_throttle_batch / collect_throttle_batch:
+    // 16-byte tc_throttle records, durations already in whole seconds) is drained that way; any other limiter (the tests' models)
+    // through submit_batch / collect_batch, with ThrottleResponse::from doing the as_secs().  Same replies either way.
+    template <class L, class = void>
+    struct answers_throttle : std::false_type {};
+    template <class L>
+    struct answers_throttle<L, std::void_t<decltype(std::declval<L&>().collect_throttle_batch())>> : std::true_type {};
+
     // actor.rs:238-255 for a whole batch, first half: hand the batch to the limiter.  false: it could not be
     // submitted and every request has been answered with the error.
     static bool submit_throttle_batch(Limiter& limiter, std::deque<RateLimiterMessage>& msgs) {
         try {
-            limiter.submit_batch(requests_of(msgs));
+            if constexpr (answers_throttle<Limiter>::value) limiter.submit_throttle_batch(requests_of(msgs));
+            else limiter.submit_batch(requests_of(msgs));
             return true;
         } catch (const std::exception& ex) {
             answer_all(msgs, std::string("Rate limit check failed: internal error: ") + ex.what());
@@ -381,21 +390,22 @@ class BasicRateLimiterActor {
 
     // second half: the replies; send errors are ignored like in the reference (the receiver may have given
     // up, actor.rs:229-230)
+    static ThrottleResponse response_of(const std::pair<bool, RateLimitResult>& ok) { return ThrottleResponse::from(ok.first, ok.second); }
+    static ThrottleResponse response_of(const ThrottleRecord& ok) { return ThrottleResponse{ok.allowed, ok.limit, ok.remaining, ok.reset_after, ok.retry_after}; }
     static void answer_throttle_batch(Limiter& limiter, std::deque<RateLimiterMessage>& msgs, std::atomic<uint64_t>* ns_collect) {
-        std::vector<RateLimitOutcome> out;
+        using Outcome = std::conditional_t<answers_throttle<Limiter>::value, ThrottleOutcome, RateLimitOutcome>;
+        std::vector<Outcome> out;
         try {
             const uint64_t t0 = clock_ns();
-            out = limiter.collect_batch();
+            if constexpr (answers_throttle<Limiter>::value) out = limiter.collect_throttle_batch();
+            else out = limiter.collect_batch();
             *ns_collect += clock_ns() - t0;
         } catch (const std::exception& ex) {
             answer_all(msgs, std::string("Rate limit check failed: internal error: ") + ex.what());
             return;
         }
-        auto reply = [](const RateLimitOutcome& o) -> Result<ThrottleResponse> {
-            if (throttlecrab::is_ok(o)) {
-                const auto& ok = std::get<0>(o);
-                return ThrottleResponse::from(ok.first, ok.second);
-            }
+        auto reply = [](const Outcome& o) -> Result<ThrottleResponse> {
+            if (throttlecrab::is_ok(o)) return response_of(std::get<0>(o));
             return "Rate limit check failed: " + std::get<1>(o).to_string();
         };
         size_t at = 0;
@@ -407,8 +417,8 @@ class BasicRateLimiterActor {
                 std::vector<Result<ThrottleResponse>> rs;
                 rs.reserve(k);
                 for (size_t i = 0; i < k; ++i) { // (in place: a temporary variant would be moved through its visitor)
-                    const RateLimitOutcome& o = out[at++];
-                    if (const auto* ok = std::get_if<0>(&o)) rs.emplace_back(std::in_place_index<0>, ThrottleResponse::from(ok->first, ok->second));
+                    const Outcome& o = out[at++];
+                    if (const auto* ok = std::get_if<0>(&o)) rs.emplace_back(std::in_place_index<0>, response_of(*ok));
                     else rs.push_back(reply(o));
                 }
                 m.many->tx.set_value(std::move(rs));

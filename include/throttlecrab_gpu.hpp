@@ -55,6 +55,17 @@ struct RateLimitResult {
     Duration retry_after;
 };
 
+// ThrottleResponse (throttlecrab-server/src/types.rs:74-96): what every transport answers with -- durations in whole seconds
+struct ThrottleRecord {
+    bool allowed;
+    int64_t limit;
+    int64_t remaining;
+    int64_t reset_after;
+    int64_t retry_after;
+};
+using ThrottleOutcome = std::variant<ThrottleRecord, CellError>;
+inline bool is_ok(const ThrottleOutcome& o) { return o.index() == 0; }
+
 // Result<(bool, RateLimitResult), CellError>
 using RateLimitOutcome = std::variant<std::pair<bool, RateLimitResult>, CellError>;
 inline bool is_ok(const RateLimitOutcome& o) { return o.index() == 0; }
@@ -224,38 +235,33 @@ class RateLimiter {
             return out;
         }
         // (up to 1024 requests the engine answers with one launch, ~35-45 us; beyond that with its pipeline)
-        std::vector<uint8_t> arena;
-        std::vector<uint32_t> off(n + 1, 0);
-        std::vector<int64_t> burst(n), count(n), period(n), qty(n), now(n);
+        std::vector<int64_t> burst, qty;
         std::vector<tc_decision> dec(n); // one 32-byte record per request; `limit` == the request's max_burst
-        for (size_t i = 0; i < n; ++i) {
-            arena.insert(arena.end(), reqs[i].key.begin(), reqs[i].key.end());
-            off[i + 1] = (uint32_t)arena.size();
-            burst[i] = reqs[i].max_burst;
-            count[i] = reqs[i].count_per_period;
-            period[i] = reqs[i].period;
-            qty[i] = reqs[i].quantity;
-            now[i] = to_ns(reqs[i].now);
-        }
-        if (arena.empty()) arena.push_back(0);
-        tc_batch b{};
-        b.struct_size = sizeof b;
-        b.n = n;
-        b.key_bytes = arena.data();
-        b.key_off = off.data();
-        b.max_burst = burst.data();
-        b.count_per_period = count.data();
-        b.period = period.data();
-        b.quantity = qty.data();
-        b.now_ns = now.data();
-        b.decisions = dec.data();
-        int rc = tc_rate_limit_batch_keys(store_.handle(), &b);
+        const int rc = run_batch(reqs, burst, qty, dec.data(), nullptr);
         for (size_t i = 0; i < n; ++i) {
             if (rc != TC_E_OK && rc != TC_E_TABLE_FULL)
                 out.push_back(CellError{CellError::Internal, 0, tc_last_error(store_.handle())});
             else
                 out.push_back(outcome(dec[i].status, dec[i].allowed, burst[i], dec[i].remaining, dec[i].reset_after_ns,
                                       dec[i].retry_after_ns, qty[i]));
+        }
+        return out;
+    }
+
+    // rate_limit_batch answered the way the transports answer: the engine returns 16-byte tc_throttle records (whole seconds)
+    // instead of 32-byte decisions; `limit` is the request's own max_burst (types.rs:88)
+    std::vector<ThrottleOutcome> throttle_batch(const std::vector<Request>& reqs) {
+        const size_t n = reqs.size();
+        std::vector<ThrottleOutcome> out;
+        out.reserve(n);
+        if (!n) return out;
+        std::vector<int64_t> burst, qty;
+        std::vector<tc_throttle> thr(n + 1); // (+ 1: room to start at a 16-byte boundary)
+        tc_throttle* t = reinterpret_cast<tc_throttle*>((reinterpret_cast<uintptr_t>(thr.data()) + 15u) & ~uintptr_t(15));
+        const int rc = run_batch(reqs, burst, qty, nullptr, t);
+        for (size_t i = 0; i < n; ++i) {
+            if (rc != TC_E_OK && rc != TC_E_TABLE_FULL) out.push_back(CellError{CellError::Internal, 0, tc_last_error(store_.handle())});
+            else out.push_back(throttle_outcome(t[i], burst[i], qty[i]));
         }
         return out;
     }
@@ -269,7 +275,16 @@ class RateLimiter {
     static constexpr size_t FLIGHTS = 3;
     static constexpr size_t SMALL_BATCH = 1024; // what the engine serves with one launch (k_small_batch)
     size_t in_flight() const { return order_.size(); }
-    void submit_batch(const std::vector<Request>& reqs) {
+    void submit_batch(const std::vector<Request>& reqs) { submit(reqs, false); }
+    std::vector<RateLimitOutcome> collect_batch() { return std::move(collect(false).ready); }
+    // the same pair answered as ThrottleResponses: the batch comes back as 16-byte tc_throttle records (what the actor drains with)
+    void submit_throttle_batch(const std::vector<Request>& reqs) { submit(reqs, true); }
+    std::vector<ThrottleOutcome> collect_throttle_batch() { return std::move(collect(true).ready_thr); }
+
+    GpuStore& store() { return store_; }
+
+  private:
+    void submit(const std::vector<Request>& reqs, bool throttle) {
         if (order_.size() >= FLIGHTS) throw std::logic_error("submit_batch: collect_batch() first");
         const size_t n = reqs.size();
         if (n > store_.max_batch()) throw std::invalid_argument("submit_batch: more requests than the store's max_batch");
@@ -283,12 +298,15 @@ class RateLimiter {
         }
         f.n = n;
         f.ready.clear();
+        f.ready_thr.clear();
+        f.throttle = throttle;
         f.rc = TC_E_OK;
         f.async = false;
         f.busy = true;
         order_.push_back(fi);
         if (n <= SMALL_BATCH) { // lightly loaded: the engine's one-launch path, answered at once (it runs behind
-            f.ready = rate_limit_batch(reqs); // the batches in flight, in stream order)
+            if (throttle) f.ready_thr = throttle_batch(reqs); // the batches in flight, in stream order)
+            else f.ready = rate_limit_batch(reqs);
             return;
         }
         uint32_t at = 0;
@@ -325,40 +343,76 @@ class RateLimiter {
             b.quantity = f.col[3];
         }
         b.now_ns = f.col[4];
-        b.decisions = f.dec;
-        f.rc = tc_rate_limit_batch_keys(store_.handle(), &b);
+        if (!throttle) b.decisions = f.dec;
+        f.rc = throttle ? tc_throttle_batch_keys(store_.handle(), &b, f.thr) : tc_rate_limit_batch_keys(store_.handle(), &b);
         f.async = f.rc == TC_E_OK;
         if (!f.async) f.err = tc_last_error(store_.handle());
     }
-    std::vector<RateLimitOutcome> collect_batch() {
+    // the oldest flight, answered into its `ready` (decisions) or `ready_thr` (throttle records), as it was submitted
+    struct Flight;
+    Flight& collect(bool throttle) {
         if (order_.empty()) throw std::logic_error("collect_batch: nothing in flight");
         Flight& f = flights_[order_.front()];
+        if (f.throttle != throttle) throw std::logic_error("collect_batch: the oldest batch was submitted in the other form");
         order_.pop_front();
-        std::vector<RateLimitOutcome> out;
-        out.reserve(f.n);
+        const size_t n = f.n;
+        auto all = [&](const CellError& err) {
+            if (throttle) f.ready_thr.assign(n, ThrottleOutcome(err));
+            else f.ready.assign(n, RateLimitOutcome(err));
+        };
         if (f.async) {
             // batches complete in submission order: everything but the younger asynchronous ones must be done
             uint32_t younger = 0;
             for (size_t fi : order_) younger += flights_[fi].async ? 1u : 0u;
             const int rc = tc_wait_batches(store_.handle(), younger);
-            for (size_t i = 0; i < f.n; ++i) {
-                if (rc != TC_E_OK) out.push_back(CellError{CellError::Internal, 0, tc_last_error(store_.handle())});
-                else
-                    out.push_back(outcome(f.dec[i].status, f.dec[i].allowed, f.col[0][i], f.dec[i].remaining, f.dec[i].reset_after_ns,
-                                          f.dec[i].retry_after_ns, f.col[3][i]));
+            if (rc != TC_E_OK) all(CellError{CellError::Internal, 0, tc_last_error(store_.handle())});
+            else if (throttle) {
+                f.ready_thr.reserve(n);
+                for (size_t i = 0; i < n; ++i) f.ready_thr.push_back(throttle_outcome(f.thr[i], f.col[0][i], f.col[3][i]));
+            } else {
+                f.ready.reserve(n);
+                for (size_t i = 0; i < n; ++i)
+                    f.ready.push_back(outcome(f.dec[i].status, f.dec[i].allowed, f.col[0][i], f.dec[i].remaining, f.dec[i].reset_after_ns,
+                                              f.dec[i].retry_after_ns, f.col[3][i]));
             }
         } else if (f.rc != TC_E_OK) {
-            for (size_t i = 0; i < f.n; ++i) out.push_back(CellError{CellError::Internal, 0, f.err});
-        } else {
-            out = std::move(f.ready);
+            all(CellError{CellError::Internal, 0, f.err});
         }
         f.busy = false;
-        return out;
+        return f;
     }
 
-    GpuStore& store() { return store_; }
+    // the requests as one synchronous key batch: decisions into `dec`, or (thr != nullptr) throttle records into `thr`
+    int run_batch(const std::vector<Request>& reqs, std::vector<int64_t>& burst, std::vector<int64_t>& qty, tc_decision* dec, tc_throttle* thr) {
+        const size_t n = reqs.size();
+        std::vector<uint8_t> arena;
+        std::vector<uint32_t> off(n + 1, 0);
+        std::vector<int64_t> count(n), period(n), now(n);
+        burst.resize(n), qty.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            arena.insert(arena.end(), reqs[i].key.begin(), reqs[i].key.end());
+            off[i + 1] = (uint32_t)arena.size();
+            burst[i] = reqs[i].max_burst;
+            count[i] = reqs[i].count_per_period;
+            period[i] = reqs[i].period;
+            qty[i] = reqs[i].quantity;
+            now[i] = to_ns(reqs[i].now);
+        }
+        if (arena.empty()) arena.push_back(0);
+        tc_batch b{};
+        b.struct_size = sizeof b;
+        b.n = n;
+        b.key_bytes = arena.data();
+        b.key_off = off.data();
+        b.max_burst = burst.data();
+        b.count_per_period = count.data();
+        b.period = period.data();
+        b.quantity = qty.data();
+        b.now_ns = now.data();
+        b.decisions = dec;
+        return thr ? tc_throttle_batch_keys(store_.handle(), &b, thr) : tc_rate_limit_batch_keys(store_.handle(), &b);
+    }
 
-  private:
     // one set of pinned staging buffers (tc_host_alloc), grown on demand while the set is idle
     struct Flight {
         uint8_t* arena = nullptr;
@@ -366,6 +420,9 @@ class RateLimiter {
         uint32_t* off = nullptr;
         int64_t* col[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
         tc_decision* dec = nullptr;
+        tc_throttle* thr = nullptr;
+        bool throttle = false;                  // submitted for throttle records (thr, ready_thr) instead of decisions (dec, ready)
+        std::vector<ThrottleOutcome> ready_thr; // small batches answered at once
         // TC_B_PLAN_DICT: the batch's dictionary (pinned, 65 536 triples), its plan ids and u32 quantities; the encoder's table
         int64_t* dict = nullptr;
         uint16_t* plan_id = nullptr;
@@ -382,7 +439,8 @@ class RateLimiter {
         Flight& operator=(const Flight&) = delete;
         Flight(Flight&& o) noexcept { *this = std::move(o); }
         Flight& operator=(Flight&& o) noexcept {
-            std::swap(arena, o.arena), std::swap(arena_cap, o.arena_cap), std::swap(off, o.off), std::swap(dec, o.dec);
+            std::swap(arena, o.arena), std::swap(arena_cap, o.arena_cap), std::swap(off, o.off), std::swap(dec, o.dec), std::swap(thr, o.thr);
+            std::swap(throttle, o.throttle), std::swap(ready_thr, o.ready_thr);
             std::swap(dict, o.dict), std::swap(plan_id, o.plan_id), std::swap(qty32, o.qty32), std::swap(plans, o.plans), std::swap(plan_of, o.plan_of);
             for (int j = 0; j < 5; ++j) std::swap(col[j], o.col[j]);
             std::swap(rows, o.rows), std::swap(n, o.n), std::swap(ready, o.ready), std::swap(err, o.err);
@@ -390,7 +448,7 @@ class RateLimiter {
             return *this;
         }
         ~Flight() {
-            tc_host_free(arena), tc_host_free(off), tc_host_free(dec);
+            tc_host_free(arena), tc_host_free(off), tc_host_free(dec), tc_host_free(thr);
             tc_host_free(dict), tc_host_free(plan_id), tc_host_free(qty32);
             for (int64_t* c : col) tc_host_free(c);
         }
@@ -430,7 +488,8 @@ class RateLimiter {
         }
         void reserve(size_t max_rows, size_t arena_bytes) {
             if (rows < max_rows) {
-                tc_host_free(off), tc_host_free(dec);
+                tc_host_free(off), tc_host_free(dec), tc_host_free(thr);
+                off = nullptr, dec = nullptr, thr = nullptr;
                 for (int64_t*& c : col) tc_host_free(c), c = nullptr;
                 tc_host_free(plan_id), tc_host_free(qty32);
                 plan_id = nullptr, qty32 = nullptr;
@@ -439,6 +498,7 @@ class RateLimiter {
                 qty32 = pinned<uint32_t>(max_rows);
                 off = pinned<uint32_t>(max_rows + 1);
                 dec = pinned<tc_decision>(max_rows);
+                thr = pinned<tc_throttle>(max_rows);
                 for (int64_t*& c : col) c = pinned<int64_t>(max_rows);
                 rows = max_rows;
             }
@@ -460,6 +520,16 @@ class RateLimiter {
         switch (status) {
             case TC_OK:
                 return std::make_pair(allowed != 0, RateLimitResult{limit, remaining, Duration(reset_ns), Duration(retry_ns)});
+            case TC_NEGATIVE_QUANTITY: return CellError{CellError::NegativeQuantity, quantity, {}};
+            case TC_INVALID_RATE_LIMIT: return CellError{CellError::InvalidRateLimit, 0, {}};
+            default: return CellError{CellError::Internal, 0, "outside the validated domain (see tcgpu.h)"};
+        }
+    }
+    static ThrottleOutcome throttle_outcome(const tc_throttle& t, int64_t limit, int64_t quantity) {
+        switch (tc_throttle_status(&t)) {
+            case TC_OK:
+                return ThrottleRecord{tc_throttle_allowed(&t) != 0, limit, (int64_t)tc_throttle_remaining(&t), (int64_t)tc_throttle_reset_after_s(&t),
+                                      (int64_t)tc_throttle_retry_after_s(&t)};
             case TC_NEGATIVE_QUANTITY: return CellError{CellError::NegativeQuantity, quantity, {}};
             case TC_INVALID_RATE_LIMIT: return CellError{CellError::InvalidRateLimit, 0, {}};
             default: return CellError{CellError::Internal, 0, "outside the validated domain (see tcgpu.h)"};

@@ -290,7 +290,10 @@ class Pipeline {
     // Returns the engine's return code (TC_E_OK, or TC_E_TABLE_FULL: those keys answer with an error).
     int run(tc_engine* e, std::string& out) {
         const size_t n = throttles();
-        std::vector<tc_decision> dec(n); // one 32-byte record per THROTTLE; `limit` is the command's max_burst
+        // one 16-byte tc_throttle record per THROTTLE: the reply's durations are whole seconds (types.rs:90-91), which is what
+        // the record carries; `limit` is the command's max_burst
+        std::vector<tc_throttle> buf(n + 1); // (+ 1: room to start at a 16-byte boundary)
+        const tc_throttle* thr = reinterpret_cast<const tc_throttle*>((reinterpret_cast<uintptr_t>(buf.data()) + 15u) & ~uintptr_t(15));
         int rc = TC_E_OK;
         if (n) {
             if (key_bytes.empty()) key_bytes.push_back(0);
@@ -305,8 +308,7 @@ class Pipeline {
             b.period = period.data();
             b.quantity = quantity.data();
             b.now_ns = now_ns.data();
-            b.decisions = dec.data();
-            rc = tc_rate_limit_batch_keys(e, &b);
+            rc = tc_throttle_batch_keys(e, &b, const_cast<tc_throttle*>(thr));
         }
         const bool usable = rc == TC_E_OK || rc == TC_E_TABLE_FULL;
         for (const Cmd& c : cmds_) {
@@ -317,17 +319,17 @@ class Pipeline {
             const size_t i = (size_t)c.throttle;
             if (!usable) {
                 put_error(out, std::string("ERR Rate limit check failed: internal error: ") + tc_last_error(e));
-            } else if (dec[i].status == TC_OK) {
+            } else if (tc_throttle_status(&thr[i]) == TC_OK) {
                 // [allowed, limit, remaining, reset_after s, retry_after s] (mod.rs:274-283, types.rs:87-96)
                 out += "*5\r\n";
-                put_integer(out, dec[i].allowed ? 1 : 0);
+                put_integer(out, tc_throttle_allowed(&thr[i]));
                 put_integer(out, max_burst[i]);
-                put_integer(out, dec[i].remaining);
-                put_integer(out, dec[i].reset_after_ns / 1000000000LL);
-                put_integer(out, dec[i].retry_after_ns / 1000000000LL);
-            } else if (dec[i].status == TC_NEGATIVE_QUANTITY) { // CellError Display (core/mod.rs:58-66)
+                put_integer(out, (int64_t)tc_throttle_remaining(&thr[i]));
+                put_integer(out, (int64_t)tc_throttle_reset_after_s(&thr[i]));
+                put_integer(out, (int64_t)tc_throttle_retry_after_s(&thr[i]));
+            } else if (tc_throttle_status(&thr[i]) == TC_NEGATIVE_QUANTITY) { // CellError Display (core/mod.rs:58-66)
                 put_error(out, "ERR Rate limit check failed: negative quantity: " + std::to_string(quantity[i]));
-            } else if (dec[i].status == TC_INVALID_RATE_LIMIT) {
+            } else if (tc_throttle_status(&thr[i]) == TC_INVALID_RATE_LIMIT) {
                 put_error(out, "ERR Rate limit check failed: invalid rate limit parameters");
             } else {
                 put_error(out, "ERR Rate limit check failed: internal error: outside the validated domain");

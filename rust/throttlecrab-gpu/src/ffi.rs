@@ -35,6 +35,7 @@ pub const TC_B_GROUPED_OUTPUT: u32 = 0x10;
 pub const TC_B_ASYNC: u32 = 0x20;
 pub const TC_B_OUTPUTS_IDLE: u32 = 0x40;
 pub const TC_B_PLAN_DICT: u32 = 0x80;
+pub const TC_T_WIDE: u32 = 0x8;
 
 pub const TC_ROUTE_AHEAD: u32 = 0x1;
 pub const TC_ROUTE_NO_READERS: u32 = 0x2;
@@ -221,6 +222,34 @@ pub struct tc_decision {
     pub pad: [u8; 6],
 }
 
+/// ThrottleResponse without `limit`, durations in whole seconds, 34 bits per value (tcgpu.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct tc_throttle {
+    pub remaining_lo: u32,
+    pub reset_after_s_lo: u32,
+    pub retry_after_s_lo: u32,
+    pub bits: u32,
+}
+
+impl tc_throttle {
+    pub fn remaining(&self) -> u64 {
+        self.remaining_lo as u64 | (((self.bits >> 8) & 3) as u64) << 32
+    }
+    pub fn reset_after_s(&self) -> u64 {
+        self.reset_after_s_lo as u64 | (((self.bits >> 10) & 3) as u64) << 32
+    }
+    pub fn retry_after_s(&self) -> u64 {
+        self.retry_after_s_lo as u64 | (((self.bits >> 12) & 3) as u64) << 32
+    }
+    pub fn allowed(&self) -> bool {
+        self.bits & 1 != 0
+    }
+    pub fn status(&self) -> u8 {
+        ((self.bits >> 1) & 3) as u8
+    }
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct tc_result {
@@ -270,6 +299,8 @@ extern "C" {
     pub fn tc_register_params_uniform(e: *mut tc_engine, max_burst: i64, count_per_period: i64, period: i64) -> c_int;
     pub fn tc_rate_limit_batch_slots(e: *mut tc_engine, b: *const tc_batch) -> c_int;
     pub fn tc_rate_limit_batch_keys(e: *mut tc_engine, b: *const tc_batch) -> c_int;
+    pub fn tc_throttle_batch_slots(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
+    pub fn tc_throttle_batch_keys(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
     pub fn tc_wait_batches(e: *mut tc_engine, max_in_flight: u32) -> c_int;
     pub fn tc_host_alloc(bytes: usize) -> *mut c_void;
     pub fn tc_host_free(p: *mut c_void);

@@ -173,6 +173,31 @@ fn decode(r: &ffi::tc_decision, limit: i64, quantity: i64) -> Result<(bool, Rate
     }
 }
 
+/// What every transport of the reference answers with (throttlecrab-server/src/types.rs:74-96): durations in whole seconds.
+#[derive(Debug, Clone, PartialEq, Eq)]
+pub struct ThrottleOutcome {
+    pub allowed: bool,
+    pub limit: i64,
+    pub remaining: i64,
+    pub reset_after: i64,
+    pub retry_after: i64,
+}
+
+fn decode_throttle(t: &ffi::tc_throttle, limit: i64, quantity: i64) -> Result<ThrottleOutcome, CellError> {
+    match t.status() {
+        ffi::TC_OK => Ok(ThrottleOutcome {
+            allowed: t.allowed(),
+            limit,
+            remaining: t.remaining() as i64,
+            reset_after: t.reset_after_s() as i64,
+            retry_after: t.retry_after_s() as i64,
+        }),
+        ffi::TC_NEGATIVE_QUANTITY => Err(CellError::NegativeQuantity(quantity)),
+        ffi::TC_INVALID_RATE_LIMIT => Err(CellError::InvalidRateLimit),
+        _ => Err(CellError::Internal("outside the engine's validated domain".into())),
+    }
+}
+
 // single owner, like the store (the pinned staging is plain memory owned by this value)
 unsafe impl Send for GpuRateLimiter {}
 
@@ -223,17 +248,54 @@ impl GpuRateLimiter {
         out
     }
 
+    /// `rate_limit_batch` answered the way the transports answer (ThrottleResponse: whole seconds): the engine returns 16-byte
+    /// tc_throttle records instead of 32-byte decisions, `limit` is the request's own max_burst.
+    pub fn throttle_batch(&mut self, reqs: &[Request]) -> Vec<Result<ThrottleOutcome, CellError>> {
+        let mut out = Vec::with_capacity(reqs.len());
+        for chunk in reqs.chunks(self.store.max_batch.max(1)) {
+            let n = chunk.len();
+            let rc = self.submit_chunk(chunk, true);
+            if rc != 0 && rc != ffi::TC_E_TABLE_FULL {
+                let msg = call_error(self.store.e, rc);
+                out.extend((0..n).map(|_| Err(CellError::Internal(msg.clone()))));
+                continue;
+            }
+            let st = &self.staging;
+            out.extend((0..n).map(|i| unsafe { decode_throttle(&*st.thr.ptr.add(i), *st.burst.ptr.add(i), *st.qty.ptr.add(i)) }));
+        }
+        out
+    }
+
     fn batch_chunk(&mut self, reqs: &[Request], out: &mut Vec<Result<(bool, RateLimitResult), CellError>>) {
         let n = reqs.len();
         if n == 0 {
             return;
         }
+        let rc = self.submit_chunk(reqs, false);
+        if rc != 0 && rc != ffi::TC_E_TABLE_FULL {
+            // nothing was applied: every request of the chunk reports the call's failure
+            let msg = call_error(self.store.e, rc);
+            out.extend((0..n).map(|_| Err(CellError::Internal(msg.clone()))));
+            return;
+        }
+        // TC_E_TABLE_FULL: the keys that fit were applied, the others carry status Internal (with the store's cleanup policy
+        // on, the engine has already swept and applied them once more before it reports this: the table is full of LIVE keys)
+        let st = &self.staging;
+        out.extend((0..n).map(|i| unsafe { decode(&*st.dec.ptr.add(i), *st.burst.ptr.add(i), *st.qty.ptr.add(i)) }));
+    }
+
+    /// marshals a non-empty chunk and runs it: decisions into `staging.dec`, or (throttle) tc_throttle records into `staging.thr`
+    fn submit_chunk(&mut self, reqs: &[Request], throttle: bool) -> i32 {
+        let n = reqs.len();
         // The request columns are marshalled straight into PINNED staging (tc_host_alloc) that lives as long as the limiter:
         // the engine's transfers to and from pinned memory run at PCIe speed, and a large batch from pinned arrays is
         // pipelined in chunks (its inputs cross the link while earlier chunks are evaluated and their results go back);
         // pageable `Vec`s would be staged once more by the runtime, with the caller blocked meanwhile.
         let key_bytes: usize = reqs.iter().map(|r| r.key.len()).sum();
         self.staging.reserve(n, key_bytes.max(1));
+        if throttle {
+            self.staging.thr.reserve(n); // (pinned on first use: a limiter that never asks for records pays nothing)
+        }
         let st = &mut self.staging;
         let mut at = 0usize;
         // Round 6, TC_B_PLAN_DICT: a server's requests carry a handful of distinct (max_burst, count_per_period, period) triples.
@@ -299,7 +361,7 @@ impl GpuRateLimiter {
             retry_after_ns: std::ptr::null_mut(),
             status: std::ptr::null_mut(),
             result4: std::ptr::null_mut(),
-            decisions: st.dec.ptr,
+            decisions: if throttle { std::ptr::null_mut() } else { st.dec.ptr },
             order: std::ptr::null_mut(),
             n_segments: 0,
             reserved_seg: 0,
@@ -311,16 +373,11 @@ impl GpuRateLimiter {
             n_plans: if compact { (st.plans.len() / 3) as u32 } else { 0 },
             reserved_dict: 0,
         };
-        let rc = unsafe { ffi::tc_rate_limit_batch_keys(self.store.e, &b) };
-        if rc != 0 && rc != ffi::TC_E_TABLE_FULL {
-            // nothing was applied: every request of the chunk reports the call's failure
-            let msg = call_error(self.store.e, rc);
-            out.extend((0..n).map(|_| Err(CellError::Internal(msg.clone()))));
-            return;
+        if throttle {
+            unsafe { ffi::tc_throttle_batch_keys(self.store.e, &b, st.thr.ptr as *mut std::os::raw::c_void) }
+        } else {
+            unsafe { ffi::tc_rate_limit_batch_keys(self.store.e, &b) }
         }
-        // TC_E_TABLE_FULL: the keys that fit were applied, the others carry status Internal (with the store's cleanup policy
-        // on, the engine has already swept and applied them once more before it reports this: the table is full of LIVE keys)
-        out.extend((0..n).map(|i| unsafe { decode(&*st.dec.ptr.add(i), *st.burst.ptr.add(i), *st.qty.ptr.add(i)) }));
     }
 }
 
@@ -369,6 +426,7 @@ struct Staging {
     qty: Pinned<i64>,
     now: Pinned<i64>,
     dec: Pinned<ffi::tc_decision>,
+    thr: Pinned<ffi::tc_throttle>,
     // TC_B_PLAN_DICT: the chunk's dictionary (pinned), its 16-bit plan ids and u32 quantities; the encoder's map
     dict: Pinned<i64>,
     plan_id: Pinned<u16>,
@@ -380,7 +438,7 @@ struct Staging {
 impl Staging {
     fn new() -> Self {
         Staging { arena: Pinned::new(), off: Pinned::new(), burst: Pinned::new(), count: Pinned::new(), period: Pinned::new(), qty: Pinned::new(),
-                  now: Pinned::new(), dec: Pinned::new(), dict: Pinned::new(), plan_id: Pinned::new(), qty32: Pinned::new(), plans: Vec::new(),
+                  now: Pinned::new(), dec: Pinned::new(), thr: Pinned::new(), dict: Pinned::new(), plan_id: Pinned::new(), qty32: Pinned::new(), plans: Vec::new(),
                   plan_of: std::collections::HashMap::new() }
     }
     fn reserve(&mut self, n: usize, key_bytes: usize) {

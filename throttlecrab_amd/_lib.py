@@ -23,6 +23,7 @@ TC_B_DEVICE_PTRS, TC_B_REGISTERED_PARAMS, TC_B_UNIQUE_SLOTS, TC_B_INPUTS_READY, 
 TC_B_ASYNC = 0x20
 TC_B_PLAN_DICT = 0x80
 TC_B_OUTPUTS_IDLE = 0x40
+TC_T_WIDE = 0x8   # tc_throttle.bits
 TC_ROUTE_AHEAD = 0x1
 TC_ROUTE_NO_READERS = 0x2
 TC_CNT_NAMES = ("total", "allowed", "denied", "errors", "swept", "batches", "keys_inserted", "live_slots")
@@ -50,6 +51,10 @@ class tc_batch(C.Structure):
                 ("status", C.c_void_p), ("result4", C.c_void_p), ("decisions", C.c_void_p), ("order", C.c_void_p),
                 ("n_segments", C.c_uint32), ("reserved_seg", C.c_uint32), ("seg_slot", C.c_void_p), ("seg_n", C.c_void_p),
                 ("plan_dict", C.c_void_p), ("plan_id", C.c_void_p), ("quantity32", C.c_void_p), ("n_plans", C.c_uint32), ("reserved_dict", C.c_uint32)]
+
+
+class tc_throttle(C.Structure):
+    _fields_ = [("remaining_lo", C.c_uint32), ("reset_after_s_lo", C.c_uint32), ("retry_after_s_lo", C.c_uint32), ("bits", C.c_uint32)]
 
 
 class tc_forward(C.Structure):
@@ -116,6 +121,8 @@ SYMBOLS = {
     "tc_register_params_uniform": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64]),
     "tc_rate_limit_batch_slots": (C.c_int, [C.c_void_p, C.POINTER(tc_batch)]),
     "tc_rate_limit_batch_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_batch)]),
+    "tc_throttle_batch_slots": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
+    "tc_throttle_batch_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
     "tc_wait_batches": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tc_host_alloc": (C.c_void_p, [C.c_size_t]),
     "tc_host_free": (None, [C.c_void_p]),

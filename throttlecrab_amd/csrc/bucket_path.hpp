@@ -377,7 +377,7 @@ __device__ __forceinline__ void eval_step(const Params& p, const Req& rq0, uint3
         bool denied_here = false;
         if (rq.status != tc::ST_OK) {
             t.ne += 1;
-            ev::write_out(p, orow, rq, d);
+            ev::write_out<FULL>(p, orow, rq, d);
         } else {
             Cell c = FIXED ? tc::fixed_cell(raw.tat, rq.dvt) : raw;
             const Decision d0 = tc::gcra_step<FULL>(c, rq.ei, rq.dvt, rq.q, rq.now); // c = state after request 0
@@ -385,10 +385,10 @@ __device__ __forceinline__ void eval_step(const Params& p, const Req& rq0, uint3
                 // request 0 denied => state untouched => every request of the run equals request 0
                 t.nd += 1;
                 denied_here = true;
-                ev::write_out(p, orow, rq, d0);
+                ev::write_out<FULL>(p, orow, rq, d0);
             } else if (r == 0 && is_last) {
                 t.na += 1; // a key requested once in this batch
-                ev::write_out(p, orow, rq, d0);
+                ev::write_out<FULL>(p, orow, rq, d0);
                 writer = true;
                 wcell = c;
             } else if (FULL) {
@@ -396,7 +396,7 @@ __device__ __forceinline__ void eval_step(const Params& p, const Req& rq0, uint3
                 if (!f.regular) tc::invariant_failed(&p.counters[(TC_CNT_COUNT + 1) + 3]); // the host's proof was wrong: must stay 0
                 if (r == 0) {
                     t.na += 1;
-                    ev::write_out(p, orow, rq, d0);
+                    ev::write_out<FULL>(p, orow, rq, d0);
                     writer = f.n_tot == 1;
                     wcell = c;
                 } else {
@@ -408,7 +408,7 @@ __device__ __forceinline__ void eval_step(const Params& p, const Req& rq0, uint3
                     t.na += d.allowed;
                     t.nd += !d.allowed;
                     denied_here = !d.allowed;
-                    ev::write_out(p, orow, rq, d);
+                    ev::write_out<FULL>(p, orow, rq, d);
                     writer = d.allowed && (is_last || (int64_t)r + 1 == f.n_tot);
                     wcell = s;
                 }
@@ -421,7 +421,7 @@ __device__ __forceinline__ void eval_step(const Params& p, const Req& rq0, uint3
                 t.na += ok_r;
                 t.nd += !ok_r;
                 denied_here = !ok_r;
-                ev::write_out(p, orow, rq, d);
+                ev::write_out<FULL>(p, orow, rq, d);
                 if (ok_r && (is_last || !tc::rank_allowed(f, r + 1u))) {
                     writer = true;
                     wcell = r == 0 ? c : tc::cell_after(f.new0 + (int64_t)r * f.inc, rq.dvt, rq.now);

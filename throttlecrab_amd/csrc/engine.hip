@@ -629,14 +629,16 @@ extern "C" void tc_engine_destroy(tc_engine* e) {
     for (tc_engine::SortSet& ss : e->sets) {
         if (ss.sorted) (void)hipEventDestroy(ss.sorted);
         if (ss.consumed) (void)hipEventDestroy(ss.consumed);
-        void* sp[] = {ss.bp_scratch, ss.elem_a, ss.elem_b, ss.elem_c, ss.range_totals, ss.part_table, ss.hot_dev, ss.hot_info, ss.hot_P, ss.hot_n, ss.hot_eval, ss.ws, ss.h_slot, ss.h_in[0], ss.h_in[1], ss.h_in[2], ss.h_in[3], ss.h_in[4], ss.h_key_bytes, ss.h_key_off};
+        void* sp[] = {ss.bp_scratch, ss.elem_a, ss.elem_b, ss.elem_c, ss.range_totals, ss.part_table, ss.hot_dev, ss.hot_info, ss.hot_P, ss.hot_n, ss.hot_eval, ss.ws, ss.h_slot, ss.h_in[0], ss.h_in[1], ss.h_in[2], ss.h_in[3], ss.h_in[4], ss.h_key_bytes, ss.h_key_off,
+                      ss.h_dict, ss.h_plan_id, ss.h_q32}; // (the last three: TC_B_PLAN_DICT staging)
         for (void* p : sp)
             if (p) (void)hipFree(p);
     }
     void* ptrs[] = {e->route_ws, e->bp_park, e->cells, e->tat8, e->rate_id, e->classes, e->denied, e->topk_ws, e->probe_ws, e->probe_stamps, e->counters, e->pend, e->chain, e->loaded, e->pend_count,
                     e->allowed_tmp, e->stage.slot, e->stage.in[0], e->stage.in[1], e->stage.in[2],
                     e->stage.in[3], e->stage.in[4], e->stage.allowed, e->stage.bits, e->stage.out[0],
-                    e->stage.out[1], e->stage.out[2], e->stage.out[3], e->stage.status, e->stage.result4, e->stage.decisions, e->stage.order};
+                    e->stage.out[1], e->stage.out[2], e->stage.out[3], e->stage.status, e->stage.result4, e->stage.decisions, e->stage.order,
+                    e->stage.throttle, e->stage.dict, e->stage.plan_id, e->stage.q32};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (e->bp_gate_host) (void)hipHostFree(e->bp_gate_host);

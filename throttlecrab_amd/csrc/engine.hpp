@@ -264,6 +264,7 @@ struct tc_engine {
         int64_t* out[4] = {nullptr, nullptr, nullptr, nullptr};
         int64_t* result4 = nullptr;
         tc_decision* decisions = nullptr;
+        tc_throttle* throttle = nullptr;
         uint32_t* order = nullptr;
         uint8_t* status = nullptr;
         int64_t* dict = nullptr;     // TC_B_PLAN_DICT (lazy): 65 536 x 3
@@ -452,6 +453,14 @@ struct tc_engine {
         if (_trc != TC_E_OK) return _trc; \
     } while (0)
 
+// A batch as it travels through the library: the caller's tc_batch, by value, and the one output sizeof(tc_batch) has no room
+// for (tc_throttle_batch_*: the struct's size is part of the ABI).  A plain tc_batch converts to one without that output.
+struct Batch : tc_batch {
+    tc_throttle* throttle;
+    Batch() : tc_batch(), throttle(nullptr) {}
+    Batch(const tc_batch& b, tc_throttle* t = nullptr) : tc_batch(b), throttle(t) {}
+};
+
 // input arrays of a TC_B_ASYNC host batch, staged inside run_slots_device on the stream that groups the batch
 struct HostIn {
     const uint32_t* slot = nullptr;
@@ -499,27 +508,27 @@ inline std::vector<uint64_t> host_chunk_plan(const tc_engine* e, uint64_t n) {
     }
     return plan;
 }
-bool host_arrays_pinned(const tc_batch& b); // slots.hip: every array the batch names is device-visible host memory
+bool host_arrays_pinned(const Batch& b); // slots.hip: every array the batch names is device-visible host memory
 // bytes that cross PCIe per request of a host batch, both ways.  Chunking pays by what it overlaps: the reference-shaped call
 // (87 B) gains 370 us per 1 Mi requests, a slot batch that asks for `allowed` only (5 B) LOSES 30 (217 us against 187, tools/
 // host_slots.py: four enqueues for 5 MB of transfers) -- so only batches that move at least HOST_CHUNK_MIN_BYTES per request.
 constexpr uint64_t HOST_CHUNK_MIN_BYTES = 16;
-inline uint64_t host_bytes_per_request(const tc_batch& b) {
+inline uint64_t host_bytes_per_request(const Batch& b) {
     uint64_t in = b.slot ? 4 : 0;
     if (b.key_off && b.key_bytes && b.n) in += 4 + (uint64_t(b.key_off[b.n]) - b.key_off[0]) / b.n;
     for (const void* c : {(const void*)b.max_burst, (const void*)b.count_per_period, (const void*)b.period, (const void*)b.quantity, (const void*)b.now_ns})
         in += c ? 8 : 0;
     if (b.flags & TC_B_PLAN_DICT) in += 2 + (b.quantity32 ? 4 : 0);
-    uint64_t out = (b.allowed ? 1 : 0) + (b.status ? 1 : 0) + (b.result4 ? 32 : 0) + (b.decisions ? 32 : 0);
+    uint64_t out = (b.allowed ? 1 : 0) + (b.status ? 1 : 0) + (b.result4 ? 32 : 0) + (b.decisions ? 32 : 0) + (b.throttle ? 16 : 0);
     for (const void* c : {(const void*)b.limit, (const void*)b.remaining, (const void*)b.reset_after_ns, (const void*)b.retry_after_ns}) out += c ? 8 : 0;
     return in + out;
 }
-inline bool host_chunking_applies(const tc_engine* e, const tc_batch& b) {
+inline bool host_chunking_applies(const tc_engine* e, const Batch& b) {
     return e->host_chunk && b.n >= 2 * e->host_chunk && !(b.flags & (TC_B_DEVICE_PTRS | TC_B_ASYNC | TC_B_GROUPED_OUTPUT | TC_B_UNIQUE_SLOTS)) &&
            host_arrays_pinned(b) && host_bytes_per_request(b) >= HOST_CHUNK_MIN_BYTES;
 }
 // requests [at, at + cn) of host batch b as a batch of their own (every column and output advanced; key_off stays absolute)
-void host_sub_batch(const tc_batch& b, uint64_t at, uint64_t cn, tc_batch& c);
+void host_sub_batch(const Batch& b, uint64_t at, uint64_t cn, Batch& c);
 // wait for the last `mine` TC_B_ASYNC batches (the ones this call issued) and hand their events back to the pool
 int wait_own_async(tc_engine* e, size_t mine);
 // host arrays -> device staging on stream s: ONE copy kernel (mk::k_copy_multi) when every source is pinned host memory, else one
@@ -530,13 +539,13 @@ int stage_in_multi(tc_engine* e, const void* const* src, void* const* dst, const
 // device (one-launch small batches, retries); dict_expand_device: a DEVICE-pointer batch's, by a kernel on the engine's stream;
 // stage_compact: host arrays -> device (dict, ids, u32 quantities into the buffers given, allocated on first use) on stream s,
 // then mk::k_expand_plans into out[0..2] (and out[3] if there are u32 quantities)
-int dict_check(tc_engine* e, const tc_batch& b);
-void dict_expand_on_host(tc_engine* e, tc_batch& b);
-int dict_expand_device(tc_engine* e, tc_batch& b);
+int dict_check(tc_engine* e, const Batch& b);
+void dict_expand_on_host(tc_engine* e, Batch& b);
+int dict_expand_device(tc_engine* e, Batch& b);
 int stage_compact(tc_engine* e, const int64_t* dict, uint32_t n_plans, const uint16_t* plan_id, const uint32_t* q32, uint32_t n, hipStream_t s, int64_t*& d_dict,
                   uint16_t*& d_id, uint32_t*& d_q32, int64_t* const out[4]);
 struct Bounced {
-    tc_batch bb;
+    Batch bb;
     struct Out {
         void* user;
         const void* pinned;
@@ -545,16 +554,16 @@ struct Bounced {
     int n_out = 0;
     bool on = false;
 };
-bool bounce_in(tc_engine* e, const tc_batch& b, Bounced& bo); // false: does not apply (bo.on stays false), the batch runs as it is
+bool bounce_in(tc_engine* e, const Batch& b, Bounced& bo); // false: does not apply (bo.on stays false), the batch runs as it is
 void bounce_out(const Bounced& bo);                          // the results, from the pinned block into the caller's arrays
-int stage_outputs(tc_engine* e, const tc_batch& b, tc_batch& d);
-int copy_outputs_back(tc_engine* e, const tc_batch& b, hipStream_t s, bool by_kernel = false);
-int run_slots_device(tc_engine* e, const tc_batch& b, const HostIn* hin = nullptr);
+int stage_outputs(tc_engine* e, const Batch& b, Batch& d);
+int copy_outputs_back(tc_engine* e, const Batch& b, hipStream_t s, bool by_kernel = false);
+int run_slots_device(tc_engine* e, const Batch& b, const HostIn* hin = nullptr);
 void hot_worker_stop(tc_engine* e); // slots.hip: the hot list's maker thread (joined by tc_engine_destroy)
-int run_slots_host_staged(tc_engine* e, const tc_batch& b, uint32_t* key_error_flag = nullptr, const uint32_t* d_slot = nullptr, bool columns_staged = false);
-int finish_async(tc_engine* e, const tc_batch& b);
-bool small_batch_applies(const tc_engine* e, const tc_batch& b);
-int run_small_batch(tc_engine* e, const tc_batch& b);
+int run_slots_host_staged(tc_engine* e, const Batch& b, uint32_t* key_error_flag = nullptr, const uint32_t* d_slot = nullptr, bool columns_staged = false);
+int finish_async(tc_engine* e, const Batch& b);
+bool small_batch_applies(const tc_engine* e, const Batch& b);
+int run_small_batch(tc_engine* e, const Batch& b);
 // device staging for host-pointer batches, allocated per array on first use
 template <class T>
 inline int stage_need(tc_engine* e, T*& p, size_t count) {

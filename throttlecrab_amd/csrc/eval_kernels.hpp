@@ -71,6 +71,10 @@ struct Params {
     // round 6: runs of at least heavy_min requests are noted in heavy[] (heavy_note below); heavy_min == 0: nothing is
     unsigned long long* heavy = nullptr;
     uint32_t heavy_min = 0, heavy_tag = 0;
+    // tc_throttle_batch_*: one 16-byte record per request (whole seconds), or nullptr.  LAST, so that the kernels that never look at
+    // it (the decisions-only variants) find every other argument where it was: a field in the middle moved their scalar loads and
+    // cost k_eval_general<false, *> 36 bytes of scratch
+    tc_throttle* throttle = nullptr;
 };
 
 // Which slots are HOT?  The grouping wants to know (range_part.hpp: a slot that takes thousands of a batch's requests is peeled
@@ -180,7 +184,33 @@ __device__ __forceinline__ Req make_req_rc(const Params& p, uint32_t slot, const
     return r;
 }
 
+// tc_throttle (tcgpu.h): remaining and the two durations in whole seconds, 34 bits each -- the low words as they are, the two
+// bits above them in `bits` beside allowed and status.  Seconds = ns / 10^9 by a CONSTANT, which the compiler turns into a
+// multiply-high and a shift (no 64-bit division routine); the values are non-negative (gcra_step clamps them at 0).  A value of
+// 2^34 or more cannot occur (the header has the proof); it would be stored as 2^34 - 1 with TC_T_WIDE.
+__device__ __forceinline__ uint32_t throttle_field(uint64_t v, int shift, uint32_t& bits) {
+    const uint32_t hi = (uint32_t)(v >> 32);
+    const bool wide = hi > 3u;
+    bits |= (wide ? (3u << shift) | TC_T_WIDE : hi << shift);
+    return wide ? 0xFFFFFFFFu : (uint32_t)v;
+}
+__device__ __forceinline__ uint4 throttle_record(bool ok, int status, const Decision& d) {
+    uint32_t bits = ((ok && d.allowed) ? 1u : 0u) | ((uint32_t)status << 1);
+    uint4 t = make_uint4(0u, 0u, 0u, 0u);
+    if (ok) {
+        t.x = throttle_field((uint64_t)d.remaining, 8, bits);
+        t.y = throttle_field((uint64_t)d.reset_after / 1000000000ull, 10, bits);
+        t.z = throttle_field((uint64_t)d.retry_after / 1000000000ull, 12, bits);
+    }
+    t.w = bits;
+    return t;
+}
+
 // (returns the decision: 1 = allowed)
+// FULL: the kernel's own FULL (the batch asked for results beyond the decision).  Throttle records make a batch a full one, so
+// only those variants compile their store: in the decisions-only variants it cost 4 vector registers and, in six of them, a wave
+// per SIMD (k_eval_sorted<false, *, 2, *> 7 -> 6, k_bucket_eval<false, false, false> 5 -> 4, <false, true, true> 4 -> 3).
+template <bool FULL = true>
 __device__ __forceinline__ bool write_out(const Params& p, uint32_t i, const Req& r, const Decision& d) {
     const bool ok = r.status == tc::ST_OK;
     if (p.allowed) p.allowed[i] = (ok && d.allowed) ? 1 : 0;
@@ -201,13 +231,15 @@ __device__ __forceinline__ bool write_out(const Params& p, uint32_t i, const Req
         dr[0] = make_longlong2(ok ? d.remaining : 0, ok ? d.reset_after : 0);
         dr[1] = make_longlong2(ok ? d.retry_after : 0, flags); // allowed | status << 8, pad = 0 (little endian)
     }
+    // one 16-byte store per request; grouped rows are consecutive, so a wave then writes 1 KiB in one piece
+    if (FULL && p.throttle) *reinterpret_cast<uint4*>(p.throttle + i) = throttle_record(ok, r.status, d);
     return ok && d.allowed;
 }
 
 // LEAN batches ask for the decision bytes only (no status / limit / result columns, request order): the other
 // output pointers are then not even looked at, which keeps the kernel's scalar registers under the 80 that eight
 // 256-thread blocks per CU need (MI355X_MICROARCH.md, residency).
-template <bool LEAN>
+template <bool LEAN, bool FULL>
 __device__ __forceinline__ bool put_out(const Params& p, uint32_t i, const Req& r, const Decision& d) {
     if (LEAN) {
         const bool a = r.status == tc::ST_OK && d.allowed;
@@ -215,7 +247,7 @@ __device__ __forceinline__ bool put_out(const Params& p, uint32_t i, const Req& 
         if (!(p.flags & (a ? (F_PREFILL1 | F_DEBUG_NOSTORE) : (F_PREFILL0 | F_DEBUG_NOSTORE)))) p.allowed[i] = a ? 1 : 0;
         return a;
     }
-    return write_out(p, i, r, d);
+    return write_out<FULL>(p, i, r, d);
 }
 
 // The resident state of `slot` under either layout.  TC_CFG_FIXED_PARAMS engines keep one TAT per key
@@ -336,7 +368,7 @@ __global__ __launch_bounds__(BLOCK) void k_eval_unique(Params p) {
         } else {
             ne = 1;
         }
-        write_out(p, i, r, d);
+        write_out<FULL>(p, i, r, d);
         if (p.order) p.order[i] = i;
     }
     block_count3(na, nd, ne, p.counters);
@@ -672,7 +704,7 @@ __device__ __forceinline__ void eval_sorted_body(const Params& p, const uint64_t
             d.remaining = d.reset_after = d.retry_after = 0;
             if (rq.status != tc::ST_OK) {
                 ne += 1;
-                put_out<LEAN>(p, orow, rq, d);
+                put_out<LEAN, FULL>(p, orow, rq, d);
             } else {
                 Cell c = FIXED ? tc::fixed_cell(cell[j].tat, rq.dvt) : cell[j];
                 const Decision d0 = tc::gcra_step<FULL>(c, rq.ei, rq.dvt, rq.q, rq.now); // c = cell after request 0
@@ -680,10 +712,10 @@ __device__ __forceinline__ void eval_sorted_body(const Params& p, const uint64_t
                     // request 0 denied => state untouched => every request of the run equals request 0
                     nd += 1;
                     denied_here[j] = true;
-                    bit = put_out<LEAN>(p, orow, rq, d0);
+                    bit = put_out<LEAN, FULL>(p, orow, rq, d0);
                 } else if (head[j] && is_last[j]) {
                     na += 1; // a key requested once in this batch: no closed form, no 64-bit division
-                    bit = put_out<LEAN>(p, orow, rq, d0);
+                    bit = put_out<LEAN, FULL>(p, orow, rq, d0);
                     writer[j] = true;
                     wcell[j] = c;
                 } else {
@@ -716,7 +748,7 @@ __device__ __forceinline__ void eval_sorted_body(const Params& p, const uint64_t
                     }
                     if (r == 0) {
                         na += 1;
-                        bit = put_out<LEAN>(p, orow, rq, d0);
+                        bit = put_out<LEAN, FULL>(p, orow, rq, d0);
                         if (regular || is_last[j]) {
                             writer[j] = owner || is_last[j];
                             wcell[j] = c;
@@ -730,7 +762,7 @@ __device__ __forceinline__ void eval_sorted_body(const Params& p, const uint64_t
                                 const Decision dj = tc::gcra_step<FULL>(c, rq.ei, rq.dvt, rq.q, rq.now);
                                 na += dj.allowed;
                                 wd += !dj.allowed;
-                                put_out<LEAN>(p, (!LEAN && p.order) ? q : (uint32_t)nx, rq, dj);
+                                put_out<LEAN, FULL>(p, (!LEAN && p.order) ? q : (uint32_t)nx, rq, dj);
                             }
                             nd += wd;
                             if (p.denied && wd) atomicAdd(&p.denied[slot], wd); // the whole run's denials sit in this lane
@@ -741,7 +773,7 @@ __device__ __forceinline__ void eval_sorted_body(const Params& p, const uint64_t
                         na += ok_r;
                         nd += !ok_r;
                         denied_here[j] = !ok_r;
-                        bit = put_out<LEAN>(p, orow, rq, d);
+                        bit = put_out<LEAN, FULL>(p, orow, rq, d);
                         writer[j] = owner;
                         wcell[j] = v;
                     }
@@ -1015,7 +1047,7 @@ __device__ __forceinline__ void write_out_general(const Params& p, uint32_t i, c
         if (!(p.flags & (a ? F_PREFILL1 : F_PREFILL0))) p.allowed[i] = a ? 1 : 0;
         return;
     }
-    write_out(p, i, r, d);
+    write_out<FULL>(p, i, r, d);
 }
 
 // RUNS (round 6): the allowed-runs rule compiled in.  A stream whose keys are drained -- most requests denied, what a skewed

@@ -202,7 +202,7 @@ static void remember_errors(tc_engine* e, uint64_t k) {
 // key table shows as status Internal on the affected requests; the TC_E_TABLE_FULL return code is delivered
 // by the next synchronous key call.  (Staging on the auxiliary stream that will group the batch, to overlap
 // the transfer with the previous batch's key stage, measured slower: 1.5 vs 2.0 G decisions/s.)
-static int run_keys_host_async(tc_engine* e, const tc_batch& b) {
+static int run_keys_host_async(tc_engine* e, const Batch& b) {
     const uint32_t n = (uint32_t)b.n;
     TC_TRY(ensure_side_streams(e));
     const bool piped = e->key_stream != nullptr && e->n_aux != 0;
@@ -237,7 +237,7 @@ static int run_keys_host_async(tc_engine* e, const tc_batch& b) {
     // (the engine cleans by itself: a synchronous caller may have to apply rejected requests again -- it needs the slots)
     if (e->as.chunk_slots_at != UINT64_MAX)
         TC_HIP(e, hipMemcpyAsync(e->k_slot + e->as.chunk_slots_at, ss.k_slot, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ks));
-    tc_batch d = b;
+    Batch d = b;
     d.flags = (b.flags & ~(TC_B_ASYNC | TC_B_INPUTS_READY)) | TC_B_DEVICE_PTRS | (piped ? TC_B_INPUTS_READY : 0u);
     d.slot = ss.k_slot;
     d.key_bytes = nullptr;
@@ -261,13 +261,13 @@ static int run_keys_host_async(tc_engine* e, const tc_batch& b) {
 }
 
 // a large synchronous host-pointer key batch, pipelined in chunks (engine.hpp: HOST_CHUNK_MIN)
-static int run_keys_host_chunked(tc_engine* e, const tc_batch& b) {
+static int run_keys_host_chunked(tc_engine* e, const Batch& b) {
     size_t mine = 0;
     int rc = TC_E_OK;
     uint64_t at = 0;
     for (const uint64_t cn : host_chunk_plan(e, b.n)) {
         if (rc != TC_E_OK) break;
-        tc_batch c;
+        Batch c;
         host_sub_batch(b, at, cn, c);
         e->as.chunk_slots_at = auto_sweep_on(e) ? at : UINT64_MAX;
         rc = run_keys_host_async(e, c);
@@ -286,7 +286,7 @@ static int run_keys_host_chunked(tc_engine* e, const tc_batch& b) {
 }
 
 // a validated key batch through the path its flags name
-static int keys_batch_dispatch(tc_engine* e, const tc_batch& b) {
+static int keys_batch_dispatch(tc_engine* e, const Batch& b) {
     if (b.flags & TC_B_ASYNC) return run_keys_host_async(e, b);
     if (host_chunking_applies(e, b)) return run_keys_host_chunked(e, b);
     const uint8_t* d_bytes = b.key_bytes;
@@ -315,7 +315,7 @@ static int keys_batch_dispatch(tc_engine* e, const tc_batch& b) {
         int rc = stage_keys(e, b.key_bytes, b.key_off, b.n, &d_bytes, &d_off, &b);
         if (rc != TC_E_OK) return rc;
     }
-    tc_batch s = b;
+    Batch s = b;
     s.key_bytes = nullptr;
     s.key_off = nullptr;
     if (dev) {
@@ -358,7 +358,8 @@ static int keys_batch_dispatch(tc_engine* e, const tc_batch& b) {
 // turned away once more.  They are exactly the requests whose key got no slot -- every request of such a key, so the
 // sub-batch, in index order, IS the tail of those keys' sequences (keys are independent) -- and they touched no state.
 // `small`: the batch went through k_small_batch (its resolved slots are in the pinned block), else through the pipeline (e->k_slot).
-static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
+static int batch_keys(tc_engine* e, const tc_batch* bp, tc_throttle* out);
+static int retry_rejected(tc_engine* e, const Batch& b0, bool small) {
     const size_t n = b0.n;
     std::vector<uint32_t> slots(n);
     if (small) {
@@ -369,7 +370,7 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
     }
     // (TC_B_PLAN_DICT: the rejected requests go round again in the wide form -- the caller's arrays are only read)
     std::vector<int64_t> wide[4];
-    tc_batch bw = b0;
+    Batch bw = b0;
     if (bw.flags & TC_B_PLAN_DICT) {
         for (int j = 0; j < 3; ++j) wide[j].resize(n);
         for (size_t i = 0; i < n; ++i) {
@@ -385,7 +386,7 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
         bw.flags &= ~TC_B_PLAN_DICT;
         bw.plan_dict = nullptr, bw.plan_id = nullptr, bw.quantity32 = nullptr, bw.n_plans = 0;
     }
-    const tc_batch& b = bw;
+    const Batch& b = bw;
     std::vector<uint32_t> idx;
     for (size_t i = 0; i < n; ++i)
         if (slots[i] == kt::NO_SLOT) idx.push_back((uint32_t)i);
@@ -417,7 +418,7 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
             sub_in[j].resize(m);
             for (size_t k = 0; k < m; ++k) sub_in[j][k] = in_cols[j][idx[k]];
         }
-    tc_batch sub = b;
+    Batch sub = b;
     sub.n = m;
     sub.key_bytes = arena.data();
     sub.key_off = off.data();
@@ -431,6 +432,8 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
     std::vector<int64_t> o_col[4], o_r4(b.result4 ? 4 * m : 0);
     for (int j = 0; j < 4; ++j) o_col[j].resize(want[j] ? m : 0);
     std::vector<tc_decision> o_dec(b.decisions ? m : 0);
+    std::vector<tc_throttle> o_thr(b.throttle ? m + 1 : 0); // (+ 1: room to start at a 16-byte boundary)
+    tc_throttle* const o_thr16 = b.throttle ? reinterpret_cast<tc_throttle*>(((uintptr_t)o_thr.data() + 15u) & ~(uintptr_t)15u) : nullptr;
     sub.allowed = o_allowed.empty() ? nullptr : o_allowed.data();
     sub.allowed_bits = nullptr;
     sub.status = b.status ? o_status.data() : nullptr;
@@ -441,7 +444,7 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
     sub.result4 = b.result4 ? o_r4.data() : nullptr;
     sub.decisions = b.decisions ? o_dec.data() : nullptr;
     e->as.in_retry = true;
-    const int rc = tc_rate_limit_batch_keys(e, &sub);
+    const int rc = batch_keys(e, &sub, o_thr16);
     e->as.in_retry = false;
     if (rc != TC_E_OK && rc != TC_E_TABLE_FULL) { // (nothing more was applied; the first pass's results stand)
         remember_errors(e, m);
@@ -457,17 +460,19 @@ static int retry_rejected(tc_engine* e, const tc_batch& b0, bool small) {
             if (want[j]) want[j][i] = o_col[j][k];
         if (b.result4) memcpy(b.result4 + 4 * (size_t)i, o_r4.data() + 4 * k, 4 * sizeof(int64_t));
         if (b.decisions) b.decisions[i] = o_dec[k];
+        if (b.throttle) b.throttle[i] = o_thr16[k];
     }
     return rc;
 }
 
-extern "C" int tc_rate_limit_batch_keys(tc_engine* e, const tc_batch* bp) {
+// both entry points: `out` = the throttle records of tc_throttle_batch_keys, nullptr for tc_rate_limit_batch_keys
+static int batch_keys(tc_engine* e, const tc_batch* bp, tc_throttle* out) {
     if (!e || !bp || bp->struct_size < offsetof(tc_batch, n_segments)) return TC_E_INVALID_ARG;
     TC_CHECK_POISON(e);
     if (!e->key_mode) return fail(e, TC_E_UNSUPPORTED, "engine was created without TC_CFG_KEY_MODE");
-    tc_batch b;
-    memset(&b, 0, sizeof b);
-    memcpy(&b, bp, std::min<size_t>(bp->struct_size, sizeof b));
+    Batch b;
+    memcpy(static_cast<tc_batch*>(&b), bp, std::min<size_t>(bp->struct_size, sizeof(tc_batch)));
+    b.throttle = out;
     if (b.n_segments) return fail(e, TC_E_INVALID_ARG, "segments belong to slot batches");
     if (b.n == 0) return TC_E_OK;
     if (b.n > e->max_batch) return fail(e, TC_E_BATCH_TOO_LARGE, "batch larger than max_batch");
@@ -495,6 +500,14 @@ extern "C" int tc_rate_limit_batch_keys(tc_engine* e, const tc_batch* bp) {
     const int rc2 = auto_sweep_after(e, b.n, true, (dev && b.now_ns) ? b.now_ns + (b.n - 1) : nullptr,
                                      (!dev && b.now_ns) ? b.now_ns[b.n - 1] : b.now_ns_scalar);
     return rc2 != TC_E_OK ? rc2 : rc;
+}
+
+extern "C" int tc_rate_limit_batch_keys(tc_engine* e, const tc_batch* bp) { return batch_keys(e, bp, nullptr); }
+
+extern "C" int tc_throttle_batch_keys(tc_engine* e, const tc_batch* bp, void* out) {
+    if (!e || !bp) return TC_E_INVALID_ARG;
+    if (!out || ((uintptr_t)out & 15u)) return fail(e, TC_E_INVALID_ARG, "tc_throttle_batch_keys: `out` is NULL or not 16-byte aligned");
+    return batch_keys(e, bp, static_cast<tc_throttle*>(out));
 }
 
 extern "C" int tc_rate_limit(tc_engine* e, const uint8_t* key, size_t key_len, int64_t max_burst,

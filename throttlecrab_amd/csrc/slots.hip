@@ -38,7 +38,7 @@ static int copy_back_async(tc_engine* e, void* host, const void* dev, size_t byt
 // Round 5: pageable arrays of a synchronous batch of a few thousand requests.  hipMemcpyAsync stages pageable memory itself, a
 // blocking copy at a time (seven in, one or more out): 201 us per reference-shaped call of 4 Ki requests where the same call
 // from pinned arrays takes 77.  Two memcpys by the caller's own thread (a few hundred KB) and the pinned path are cheaper.
-bool bounce_in(tc_engine* e, const tc_batch& b, Bounced& bo) {
+bool bounce_in(tc_engine* e, const Batch& b, Bounced& bo) {
     bo.on = false;
     if (!e->bounce_max || e->fault_countdown || (b.flags & (TC_B_DEVICE_PTRS | TC_B_ASYNC | TC_B_PLAN_DICT)) || b.n_segments) return false;
     const uint64_t n = b.n;
@@ -58,6 +58,7 @@ bool bounce_in(tc_engine* e, const tc_batch& b, Bounced& bo) {
     if (b.status) room(n);
     if (b.result4) room(n * 32);
     if (b.decisions) room(n * sizeof(tc_decision));
+    if (b.throttle) room(n * sizeof(tc_throttle));
     const bool grouped = b.order && (b.flags & TC_B_GROUPED_OUTPUT);
     if (grouped) room(n * 4);
     if (need > e->bounce_max || host_arrays_pinned(b)) return false;
@@ -102,6 +103,7 @@ bool bounce_in(tc_engine* e, const tc_batch& b, Bounced& bo) {
     if (b.status) bo.bb.status = (uint8_t*)out(b.status, n);
     if (b.result4) bo.bb.result4 = (int64_t*)out(b.result4, n * 32);
     if (b.decisions) bo.bb.decisions = (tc_decision*)out(b.decisions, n * sizeof(tc_decision));
+    if (b.throttle) bo.bb.throttle = (tc_throttle*)out(b.throttle, n * sizeof(tc_throttle));
     if (grouped) bo.bb.order = (uint32_t*)out(b.order, n * 4);
     bo.on = true;
     return true;
@@ -143,7 +145,7 @@ int stage_in_multi(tc_engine* e, const void* const* src, void* const* dst, const
 }
 
 // ---- TC_B_PLAN_DICT (round 6) -----------------------------------------------------------------------------------------------
-int dict_check(tc_engine* e, const tc_batch& b) {
+int dict_check(tc_engine* e, const Batch& b) {
     if (!(b.flags & TC_B_PLAN_DICT)) return TC_E_OK;
     if (!b.plan_dict || !b.plan_id || b.n_plans == 0 || b.n_plans > 65536u) return fail(e, TC_E_INVALID_ARG, "TC_B_PLAN_DICT: plan_dict / plan_id / n_plans (1..65536)");
     if (b.max_burst || b.count_per_period || b.period) return fail(e, TC_E_INVALID_ARG, "TC_B_PLAN_DICT: max_burst / count_per_period / period columns must be NULL");
@@ -152,7 +154,7 @@ int dict_check(tc_engine* e, const tc_batch& b) {
     return TC_E_OK;
 }
 
-void dict_expand_on_host(tc_engine* e, tc_batch& b) {
+void dict_expand_on_host(tc_engine* e, Batch& b) {
     const uint64_t n = b.n;
     for (int j = 0; j < 3; ++j) e->dict_wide[j].resize(n);
     for (uint64_t i = 0; i < n; ++i) {
@@ -170,7 +172,7 @@ void dict_expand_on_host(tc_engine* e, tc_batch& b) {
     b.plan_dict = nullptr, b.plan_id = nullptr, b.quantity32 = nullptr, b.n_plans = 0;
 }
 
-int dict_expand_device(tc_engine* e, tc_batch& b) {
+int dict_expand_device(tc_engine* e, Batch& b) {
     const uint32_t n = (uint32_t)b.n;
     hipStream_t s = cur_stream(e);
     for (int j = 0; j < (b.quantity32 ? 4 : 3); ++j) TC_TRY(stage_need(e, e->stage.in[j], e->max_batch));
@@ -201,7 +203,7 @@ int stage_compact(tc_engine* e, const int64_t* dict, uint32_t n_plans, const uin
 }
 
 // output staging for the arrays `b` asks for; `d` gets the device pointers
-int stage_outputs(tc_engine* e, const tc_batch& b, tc_batch& d) {
+int stage_outputs(tc_engine* e, const Batch& b, Batch& d) {
     const uint64_t mb = e->max_batch;
     tc_engine::Stage& st = e->stage;
     if (b.allowed) TC_TRY(stage_need(e, st.allowed, mb));
@@ -212,6 +214,7 @@ int stage_outputs(tc_engine* e, const tc_batch& b, tc_batch& d) {
     if (b.status) TC_TRY(stage_need(e, st.status, mb));
     if (b.result4) TC_TRY(stage_need(e, st.result4, mb * 4));
     if (b.decisions) TC_TRY(stage_need(e, st.decisions, mb));
+    if (b.throttle) TC_TRY(stage_need(e, st.throttle, mb));
     if (b.order) TC_TRY(stage_need(e, st.order, mb));
     d.allowed = b.allowed ? st.allowed : nullptr;
     d.allowed_bits = b.allowed_bits ? st.bits : nullptr;
@@ -222,12 +225,13 @@ int stage_outputs(tc_engine* e, const tc_batch& b, tc_batch& d) {
     d.status = b.status ? st.status : nullptr;
     d.result4 = b.result4 ? st.result4 : nullptr;
     d.decisions = b.decisions ? st.decisions : nullptr;
+    d.throttle = b.throttle ? st.throttle : nullptr;
     d.order = b.order ? st.order : nullptr;
     return TC_E_OK;
 }
 
 // staged outputs -> the caller's host arrays, enqueued on `s` (by_kernel: TC_B_ASYNC, see copy_back_async)
-int copy_outputs_back(tc_engine* e, const tc_batch& b, hipStream_t s, bool by_kernel) {
+int copy_outputs_back(tc_engine* e, const Batch& b, hipStream_t s, bool by_kernel) {
     const uint64_t n = b.n;
     const tc_engine::Stage& st = e->stage;
     auto back = [&](void* host, const void* dev, size_t bytes) -> int {
@@ -243,6 +247,7 @@ int copy_outputs_back(tc_engine* e, const tc_batch& b, hipStream_t s, bool by_ke
     if (b.status) TC_TRY(back(b.status, st.status, n));
     if (b.result4) TC_TRY(back(b.result4, st.result4, n * 4 * sizeof(int64_t)));
     if (b.decisions) TC_TRY(back(b.decisions, st.decisions, n * sizeof(tc_decision)));
+    if (b.throttle) TC_TRY(back(b.throttle, st.throttle, n * sizeof(tc_throttle)));
     if (b.order && (b.flags & TC_B_GROUPED_OUTPUT)) TC_TRY(back(b.order, st.order, n * sizeof(uint32_t)));
     return TC_E_OK;
 }
@@ -250,7 +255,7 @@ int copy_outputs_back(tc_engine* e, const tc_batch& b, hipStream_t s, bool by_ke
 // every output of a synchronous host batch (+ the key table's error word, into the pinned result block) behind the evaluation in
 // one or two k_copy_multi launches; false: not applicable (an output in pageable memory, a failed copy being simulated, too many
 // bytes: TCGPU_SYNC_COPY_MAX, default 64 MB -- 0 switches this off) and nothing was enqueued
-static bool outputs_back_in_one_launch(tc_engine* e, const tc_batch& b, hipStream_t s, bool with_flag, bool* flag_done) {
+static bool outputs_back_in_one_launch(tc_engine* e, const Batch& b, hipStream_t s, bool with_flag, bool* flag_done) {
     if (e->fault_countdown || e->copy_kernel_off) return false;
     const uint64_t n = b.n;
     const tc_engine::Stage& st = e->stage;
@@ -270,6 +275,7 @@ static bool outputs_back_in_one_launch(tc_engine* e, const tc_batch& b, hipStrea
     add(b.status, st.status, n);
     add(b.result4, st.result4, n * 4 * sizeof(int64_t));
     add(b.decisions, st.decisions, n * sizeof(tc_decision));
+    add(b.throttle, st.throttle, n * sizeof(tc_throttle)); // (the tenth; `order` may follow: at most 11 of segs[12], and the second group of 8 holds 3 of them + the key-error word)
     if (b.flags & TC_B_GROUPED_OUTPUT) add(b.order, st.order, n * sizeof(uint32_t));
     size_t total = 0;
     mk::CopySegs sg[2];
@@ -287,7 +293,7 @@ static bool outputs_back_in_one_launch(tc_engine* e, const tc_batch& b, hipStrea
     }
     static const size_t limit = [] { const char* v = getenv("TCGPU_SYNC_COPY_MAX"); return v ? (size_t)strtoull(v, nullptr, 10) : (size_t)(64u << 20); }();
     if (total > limit) return false;
-    if (with_flag) { // (the last group has room: at most 10 outputs + the word)
+    if (with_flag) { // (the last group has room: at most 11 outputs + the word)
         const uint32_t g = used[0] < 8 ? 0 : 1;
         void* dv = nullptr;
         if (hipHostGetDevicePointer(&dv, e->host_results, 0) != hipSuccess) return false;
@@ -556,7 +562,7 @@ static const uint64_t* sort_by_slot(tc_engine* e, tc_engine::SortSet& ss, hipStr
 //     ei > 0,  dvt > 0 (burst >= 2: the entry outlives its own timestamp),  q > 0,
 //     ei * q < 2^62,  0 <= now,  now + dvt < 2^62,
 // checked here for the batch's scalar rate or for the bounds over all registered plans.
-static bool all_runs_regular(const tc_engine* e, const tc_batch& b, const Params& p) {
+static bool all_runs_regular(const tc_engine* e, const Batch& b, const Params& p) {
     const int64_t LIM = (int64_t)1 << 62;
     const int64_t q = p.q_s, now = p.now_s;
     if (q <= 0 || now < 0) return false;
@@ -783,7 +789,7 @@ static int stage_host_inputs(tc_engine* e, tc_engine::SortSet& ss, const HostIn&
 }
 
 // the pieces of a segmented slot column -> the scratch set's staging column, on stream `st`
-static int gather_segments(tc_engine* e, tc_engine::SortSet& ss, const tc_batch& b, uint32_t n, hipStream_t st, Params& p, const uint32_t** d_slot) {
+static int gather_segments(tc_engine* e, tc_engine::SortSet& ss, const Batch& b, uint32_t n, hipStream_t st, Params& p, const uint32_t** d_slot) {
     if (!ss.h_slot) TC_HIP(e, hipMalloc(&ss.h_slot, e->max_batch * sizeof(uint32_t)));
     mk::Segments sg;
     memset(&sg, 0, sizeof sg);
@@ -802,7 +808,7 @@ static int gather_segments(tc_engine* e, tc_engine::SortSet& ss, const tc_batch&
 }
 
 // all pointers in `b` are device pointers here (hin: the inputs are host arrays still to be staged)
-int run_slots_device(tc_engine* e, const tc_batch& b, const HostIn* hin) {
+int run_slots_device(tc_engine* e, const Batch& b, const HostIn* hin) {
     const uint32_t n = (uint32_t)b.n;
     Params p;
     p.n = n;
@@ -826,6 +832,7 @@ int run_slots_device(tc_engine* e, const tc_batch& b, const HostIn* hin) {
     p.status = b.status;
     p.result4 = b.result4;
     p.decisions = b.decisions;
+    p.throttle = b.throttle;
     p.order = (b.flags & TC_B_GROUPED_OUTPUT) ? b.order : nullptr;
     p.cells = e->cells;
     p.tat8 = e->tat8;
@@ -849,7 +856,7 @@ int run_slots_device(tc_engine* e, const tc_batch& b, const HostIn* hin) {
         p.flags |= F_REGISTERED;
         if (e->uniform_id) p.flags |= F_UNIFORM_CLASS;
     }
-    const bool full = p.remaining || p.reset || p.retry || p.result4 || p.decisions;
+    const bool full = p.remaining || p.reset || p.retry || p.result4 || p.decisions || p.throttle; // (throttle records: never the lean kernels or the rank form)
     const dim3 grid(nblocks(n)), block(BLOCK);
     hipStream_t s = cur_stream(e);
     bool bits_in_kernel = false;
@@ -1069,10 +1076,10 @@ int run_slots_device(tc_engine* e, const tc_batch& b, const HostIn* hin) {
 // key_error_flag: a key batch -- "did a key fail to get a slot" comes back with the results, behind the same wait (it used to be
 // a copy and a wait of its own behind this one: ~25 us of a 4 Ki-request call's 200)
 // d_slot: the slot column where it already is in device memory (a key batch's resolved slots), else e->stage.slot
-int run_slots_host_staged(tc_engine* e, const tc_batch& b, uint32_t* key_error_flag, const uint32_t* d_slot, bool columns_staged) {
+int run_slots_host_staged(tc_engine* e, const Batch& b, uint32_t* key_error_flag, const uint32_t* d_slot, bool columns_staged) {
     const uint64_t n = b.n;
     hipStream_t s = cur_stream(e);
-    tc_batch d = b;
+    Batch d = b;
     d.flags |= TC_B_DEVICE_PTRS;
     d.flags &= ~(TC_B_INPUTS_READY | TC_B_ASYNC);
     d.slot = d_slot ? d_slot : e->stage.slot;
@@ -1119,7 +1126,7 @@ int run_slots_host_staged(tc_engine* e, const tc_batch& b, uint32_t* key_error_f
 }
 
 // results back to the caller's arrays behind the evaluation + the batch's completion event
-int finish_async(tc_engine* e, const tc_batch& b) {
+int finish_async(tc_engine* e, const Batch& b) {
     hipStream_t s = cur_stream(e);
     TC_TRY(copy_outputs_back(e, b, s, true));
     hipEvent_t ev = nullptr;
@@ -1136,8 +1143,8 @@ int finish_async(tc_engine* e, const tc_batch& b) {
 
 // TC_B_ASYNC: the host batch's inputs are staged on the stream that groups it (overlapping the evaluation
 // of earlier batches), the outputs are copied back behind its evaluation, nothing waits.
-static int run_slots_host_async(tc_engine* e, const tc_batch& b) {
-    tc_batch d = b;
+static int run_slots_host_async(tc_engine* e, const Batch& b) {
+    Batch d = b;
     d.flags |= TC_B_DEVICE_PTRS | TC_B_INPUTS_READY; // the host arrays are complete at call time by contract
     d.flags &= ~TC_B_ASYNC;
     d.slot = nullptr;
@@ -1157,17 +1164,17 @@ static int run_slots_host_async(tc_engine* e, const tc_batch& b) {
     return finish_async(e, b);
 }
 
-bool host_arrays_pinned(const tc_batch& b) {
+bool host_arrays_pinned(const Batch& b) {
     const bool dict = (b.flags & TC_B_PLAN_DICT) != 0;
     const void* arrays[] = {b.slot, b.key_bytes, b.key_off, b.max_burst, b.count_per_period, b.period, b.quantity, b.now_ns, b.allowed, b.allowed_bits,
-                            b.limit, b.remaining, b.reset_after_ns, b.retry_after_ns, b.status, b.result4, b.decisions,
+                            b.limit, b.remaining, b.reset_after_ns, b.retry_after_ns, b.status, b.result4, b.decisions, b.throttle,
                             dict ? (const void*)b.plan_dict : nullptr, dict ? (const void*)b.plan_id : nullptr, dict ? (const void*)b.quantity32 : nullptr};
     for (const void* a : arrays)
         if (a && !device_view_of_host(a)) return false;
     return true;
 }
 
-void host_sub_batch(const tc_batch& b, uint64_t at, uint64_t cn, tc_batch& c) {
+void host_sub_batch(const Batch& b, uint64_t at, uint64_t cn, Batch& c) {
     c = b;
     c.n = cn;
     c.flags |= TC_B_ASYNC;
@@ -1189,6 +1196,7 @@ void host_sub_batch(const tc_batch& b, uint64_t at, uint64_t cn, tc_batch& c) {
     if (c.status) c.status += at;
     if (c.result4) c.result4 += 4 * at;
     if (c.decisions) c.decisions += at;
+    if (c.throttle) c.throttle += at;
 }
 
 int wait_own_async(tc_engine* e, size_t mine) {
@@ -1203,15 +1211,15 @@ int wait_own_async(tc_engine* e, size_t mine) {
     return poisoned(e);
 }
 
-static int run_slots_host_async(tc_engine* e, const tc_batch& b);
+static int run_slots_host_async(tc_engine* e, const Batch& b);
 // a large synchronous host-pointer slot batch, pipelined in chunks (engine.hpp: HOST_CHUNK_MIN)
-static int run_slots_host_chunked(tc_engine* e, const tc_batch& b) {
+static int run_slots_host_chunked(tc_engine* e, const Batch& b) {
     size_t mine = 0;
     int rc = TC_E_OK;
     uint64_t at = 0;
     for (const uint64_t cn : host_chunk_plan(e, b.n)) {
         if (rc != TC_E_OK) break;
-        tc_batch c;
+        Batch c;
         host_sub_batch(b, at, cn, c);
         rc = run_slots_host_async(e, c);
         if (rc == TC_E_OK) ++mine;
@@ -1226,7 +1234,7 @@ static int run_slots_host_chunked(tc_engine* e, const tc_batch& b) {
 // ---- small host-pointer batches: one launch (k_small_batch) ----------------------------------------
 constexpr size_t SMALL_KEY_BYTES = 128 * 1024; // string mode: batches with a larger key arena take the big pipeline
 
-bool small_batch_applies(const tc_engine* e, const tc_batch& b) {
+bool small_batch_applies(const tc_engine* e, const Batch& b) {
     if (e->small_off || b.n > (uint64_t)SMALL_MAX) return false;
     if (b.flags & (TC_B_DEVICE_PTRS | TC_B_ASYNC | TC_B_GROUPED_OUTPUT)) return false;
     if (b.allowed_bits) return false; // (packed bits come out of the big pipeline only)
@@ -1236,11 +1244,11 @@ bool small_batch_applies(const tc_engine* e, const tc_batch& b) {
 
 // Host-pointer batch of at most SMALL_MAX requests, slot or string mode.  Same results as the big pipeline
 // (the run walker is the plain sequence); ordering against key stages on the key stream as tc_rate_limit.
-int run_small_batch(tc_engine* e, const tc_batch& b) {
+int run_small_batch(tc_engine* e, const Batch& b) {
     aside_reset(e); // (resolves its keys inside the kernel, on the engine's stream)
     const size_t n = b.n;
     if (!e->small_io) {
-        const size_t bytes = 64 + SMALL_KEY_BYTES + (size_t)SMALL_MAX * (4 + 4 + 4 + 5 * 8 + 1 + 1 + 4 * 8 + 32 + 32) + 16 * 16;
+        const size_t bytes = 64 + SMALL_KEY_BYTES + (size_t)SMALL_MAX * (4 + 4 + 4 + 5 * 8 + 1 + 1 + 4 * 8 + 32 + 32 + 16) + 17 * 16;
         TC_HIP(e, hipHostMalloc((void**)&e->small_io, bytes, hipHostMallocDefault));
         void* dv = nullptr;
         TC_HIP(e, hipHostGetDevicePointer(&dv, e->small_io, 0));
@@ -1292,7 +1300,7 @@ int run_small_batch(tc_engine* e, const tc_batch& b) {
     struct Out {
         void* host;
         size_t at, bytes;
-    } outs[9];
+    } outs[10];
     int n_out = 0;
     auto out_col = [&](void* host, size_t bytes) -> uint8_t* {
         if (!host) return nullptr;
@@ -1308,6 +1316,7 @@ int run_small_batch(tc_engine* e, const tc_batch& b) {
     p.retry = (int64_t*)out_col(b.retry_after_ns, n * 8);
     p.result4 = (int64_t*)out_col(b.result4, n * 32);
     p.decisions = (tc_decision*)out_col(b.decisions, n * sizeof(tc_decision));
+    p.throttle = (tc_throttle*)out_col(b.throttle, n * sizeof(tc_throttle));
     if (off > e->small_io_bytes) return fail(e, TC_E_INVALID_ARG, "small batch does not fit its staging block");
     p.cells = e->cells;
     p.tat8 = e->tat8;
@@ -1348,13 +1357,14 @@ int run_small_batch(tc_engine* e, const tc_batch& b) {
     return TC_E_OK;
 }
 
-extern "C" int tc_rate_limit_batch_slots(tc_engine* e, const tc_batch* bp) {
+// both entry points: `out` = the throttle records of tc_throttle_batch_slots, nullptr for tc_rate_limit_batch_slots
+static int batch_slots(tc_engine* e, const tc_batch* bp, tc_throttle* out) {
     // (callers built against the struct without the segment fields pass its old size: those fields read as zero)
     if (!e || !bp || bp->struct_size < offsetof(tc_batch, n_segments)) return TC_E_INVALID_ARG;
     TC_CHECK_POISON(e);
-    tc_batch b;
-    memset(&b, 0, sizeof b);
-    memcpy(&b, bp, std::min<size_t>(bp->struct_size, sizeof b));
+    Batch b;
+    memcpy(static_cast<tc_batch*>(&b), bp, std::min<size_t>(bp->struct_size, sizeof(tc_batch)));
+    b.throttle = out;
     if (b.n == 0) return TC_E_OK;
     if (b.n > e->max_batch) return fail(e, TC_E_BATCH_TOO_LARGE, "batch larger than max_batch");
     aside_reset(e); // (a key engine's cells touched by slot: the next sweep goes behind it -- keys.hip: sweep_keys_device)
@@ -1399,7 +1409,7 @@ extern "C" int tc_rate_limit_batch_slots(tc_engine* e, const tc_batch* bp) {
     } else {
         // host pointers: stage in, run, stage out, synchronise (a small batch in pageable memory: through the engine's pinned block)
         Bounced bo;
-        const tc_batch& u = bounce_in(e, b, bo) ? bo.bb : b;
+        const Batch& u = bounce_in(e, b, bo) ? bo.bb : b;
         TC_TRY(stage_need(e, e->stage.slot, e->max_batch));
         TC_HIP(e, copy_async(e, e->stage.slot, u.slot, u.n * sizeof(uint32_t), hipMemcpyHostToDevice, cur_stream(e)));
         rc = run_slots_host_staged(e, u);
@@ -1411,6 +1421,14 @@ extern "C" int tc_rate_limit_batch_slots(tc_engine* e, const tc_batch* bp) {
     if (rc == TC_E_OK && auto_sweep_on(e))
         rc = auto_sweep_after(e, b.n, false, (dev_ptrs && b.now_ns) ? b.now_ns + (b.n - 1) : nullptr, (!dev_ptrs && b.now_ns) ? b.now_ns[b.n - 1] : b.now_ns_scalar);
     return rc;
+}
+
+extern "C" int tc_rate_limit_batch_slots(tc_engine* e, const tc_batch* bp) { return batch_slots(e, bp, nullptr); }
+
+extern "C" int tc_throttle_batch_slots(tc_engine* e, const tc_batch* bp, void* out) {
+    if (!e || !bp) return TC_E_INVALID_ARG;
+    if (!out || ((uintptr_t)out & 15u)) return fail(e, TC_E_INVALID_ARG, "tc_throttle_batch_slots: `out` is NULL or not 16-byte aligned");
+    return batch_slots(e, bp, static_cast<tc_throttle*>(out));
 }
 
 extern "C" int tc_wait_batches(tc_engine* e, uint32_t max_in_flight) {

@@ -28,7 +28,7 @@ def _is_torch(x) -> bool:
 class BatchResult:
     """Columnar (bool, RateLimitResult) + status for one batch."""
     __slots__ = ("allowed", "allowed_bits", "limit", "remaining", "reset_after_ns", "retry_after_ns", "status",
-                 "result4", "decisions", "order")
+                 "result4", "decisions", "order", "throttle")
 
     def __init__(self, **arrays):
         for s in self.__slots__:
@@ -64,6 +64,17 @@ class Engine:
     # tc_decision records: decisions[i] = remaining, reset_after_ns, retry_after_ns, allowed | status << 8
     # (everything but `limit`, which the caller knows) -- ONE scattered store per request
     DECISION_FIELDS = ("decisions",)
+    # tc_throttle records (tc_throttle_batch_*): throttle[i] = remaining, reset_after_s, retry_after_s (low words), bits -- the
+    # reference's ThrottleResponse without `limit`, durations in whole seconds: 16 bytes per request
+    THROTTLE_FIELDS = ("throttle",)
+
+    @staticmethod
+    def unpack_throttle(arr):
+        """[n, 4] uint32 throttle records -> dict of allowed, status, remaining, reset_after_s, retry_after_s (int64) and `bits`."""
+        t = (arr.cpu().numpy() if _is_torch(arr) else np.asarray(arr)).view(np.uint32).reshape(-1, 4).astype(np.int64)
+        bits = t[:, 3]
+        return {"allowed": bits & 1, "status": (bits >> 1) & 3, "remaining": t[:, 0] | (((bits >> 8) & 3) << 32),
+                "reset_after_s": t[:, 1] | (((bits >> 10) & 3) << 32), "retry_after_s": t[:, 2] | (((bits >> 12) & 3) << 32), "bits": bits}
 
     @staticmethod
     def unpack_decisions(dec):
@@ -291,6 +302,24 @@ class Engine:
             b.order = res.order.data_ptr() if _is_torch(res.order) else res.order.ctypes.data
         for name in want:
             cur = getattr(res, name)
+            if name == "throttle":  # [n, 4] uint32, 16-byte aligned; not a tc_batch field: the argument of tc_throttle_batch_*
+                if cur is not None and _is_torch(cur) != dev:
+                    raise ValueError("throttle: a CUDA tensor in a device-pointer batch, a numpy array otherwise")
+                if cur is not None and not self._is_record_array(cur, n):
+                    if async_:
+                        raise ValueError("async_: the throttle array must be a 16-byte aligned [n, 4] uint32 array (no hidden reallocation may be made)")
+                    cur = None
+                if cur is None:
+                    if dev:
+                        import torch
+                        cur = torch.empty((n, 4), dtype=torch.int32, device=f"cuda:{self.device}")
+                    else:
+                        raw = np.zeros(4 * n + 4, dtype=np.uint32)
+                        at = (-raw.ctypes.data % 16) // 4
+                        cur = raw[at:at + 4 * n].reshape(n, 4)
+                    res.throttle = cur
+                keep.append(cur)
+                continue
             ln = (n + 63) // 64 if name == "allowed_bits" else (4 * n if name in ("result4", "decisions") else n)
             if cur is not None and (cur.numel() if _is_torch(cur) else cur.size) < ln:
                 if async_:
@@ -360,10 +389,24 @@ class Engine:
             b.seg_slot = C.cast(seg_arrays[0], C.c_void_p)
             b.seg_n = C.cast(seg_arrays[1], C.c_void_p)
         if n:
-            self._check(self._lib.tc_rate_limit_batch_slots(self._h, C.byref(b)))
+            self._check(self._call_batch("slots", b, res, want))
             if async_:
                 self._async_keep.append((keep, k2))  # arrays stay referenced while the batch is in flight
         return res
+
+    @staticmethod
+    def _is_record_array(a, n) -> bool:
+        """a C-contiguous, 16-byte aligned [n, 4] array of 4-byte integers: n tc_throttle records"""
+        if _is_torch(a):
+            return tuple(a.shape) == (n, 4) and a.element_size() == 4 and not a.is_floating_point() and a.is_contiguous() and a.data_ptr() % 16 == 0
+        return a.shape == (n, 4) and a.dtype.kind in "iu" and a.dtype.itemsize == 4 and a.flags.c_contiguous and a.ctypes.data % 16 == 0
+
+    def _call_batch(self, kind, b, res, want) -> int:
+        """tc_rate_limit_batch_<kind>, or tc_throttle_batch_<kind> when the throttle records are wanted"""
+        if "throttle" not in want:
+            return getattr(self._lib, "tc_rate_limit_batch_" + kind)(self._h, C.byref(b))
+        t = res.throttle
+        return getattr(self._lib, "tc_throttle_batch_" + kind)(self._h, C.byref(b), t.data_ptr() if _is_torch(t) else t.ctypes.data)
 
     def wait_batches(self, max_in_flight: int = 0) -> None:
         """Block until at most `max_in_flight` async_ batches are still incomplete (tc_wait_batches)."""
@@ -409,7 +452,7 @@ class Engine:
         b.key_bytes = kb
         b.key_off = ko
         if n:
-            self._check(self._lib.tc_rate_limit_batch_keys(self._h, C.byref(b)))
+            self._check(self._call_batch("keys", b, res, want))
             if async_:
                 self._async_keep.append((keep, k2))
         return res

@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Where the reference-shaped call's time goes: the async ring of pinned sets at one batch size with the
-inputs / outputs switched on one by one.  ABI_N (requests per call), ABI_KEYS (table), ABI_CALLS."""
+inputs / outputs switched on one by one.  ABI_N (requests per call), ABI_KEYS (table), ABI_CALLS.
+Mode `throttle`: the call of `all` answered as 16-byte tc_throttle records (tc_throttle_batch_keys) instead of 32-byte decisions;
+ABI_REPEAT=k runs the list of modes k times over, alternating, in one process (what an A/B of two modes wants); ABI_DICT=1 sends
+the plans in the dictionary form the shims use (TC_B_PLAN_DICT: 29 bytes in per request instead of 55)."""
 import os
 import sys
 import time
@@ -17,7 +20,7 @@ from throttlecrab_amd import workload as W  # noqa: E402
 n = int(os.environ.get("ABI_N", 1 << 20))
 n_keys = int(os.environ.get("ABI_KEYS", 2_000_000))
 calls = int(os.environ.get("ABI_CALLS", 16))
-modes = os.environ.get("ABI_MODES", "all,no_out,no_cols,keys_only,sync").split(",")
+modes = os.environ.get("ABI_MODES", "all,throttle,no_out,no_cols,keys_only,sync").split(",")
 eng = t.Engine(n_keys + n, n, key_mode=True)
 import torch  # noqa: E402
 dev = torch.device("cuda:0")
@@ -34,7 +37,15 @@ for k in range(D):
     pb = {c: eng.host_alloc(batches[k][c].size, batches[k][c].dtype) for c in ("key_bytes", "key_off") + bench.ABI_COLS}
     for c in pb:
         pb[c][:] = batches[k][c]
-    pinned.append((pb, t.BatchResult(decisions=eng.host_alloc(4 * n, np.int64), allowed=eng.host_alloc(n, np.uint8))))
+    if os.environ.get("ABI_DICT", "0") == "1":
+        dic, pid = t.Engine.encode_plans(pb["max_burst"], pb["count_per_period"], pb["period"])
+        pb["plan_dict"] = tuple(eng.host_alloc(a.size, a.dtype) for a in (dic, pid, pb["quantity"].astype(np.uint32)))
+        for h, a in zip(pb["plan_dict"], (dic, pid, pb["quantity"].astype(np.uint32))):
+            h[:] = a.reshape(-1)
+    res = t.BatchResult(decisions=eng.host_alloc(4 * n, np.int64), allowed=eng.host_alloc(n, np.uint8))
+    if "throttle" in modes:
+        res.throttle = eng.host_alloc(4 * n, np.uint32).reshape(n, 4)
+    pinned.append((pb, res))
 
 
 def run(mode):
@@ -44,7 +55,9 @@ def run(mode):
         if asy:
             eng.wait_batches(D - 1)
         kw = {c: pb[c] for c in bench.ABI_COLS}
-        want = ("decisions",)
+        if "plan_dict" in pb:
+            kw = dict(now_ns=pb["now_ns"], plan_dict=pb["plan_dict"])
+        want = ("throttle",) if mode == "throttle" else ("decisions",)
         if mode in ("no_out", "keys_only"):
             want = ("allowed",)
         if mode in ("no_cols", "keys_only"):
@@ -63,8 +76,9 @@ def run(mode):
     print(f"{mode:10s} n={n}: {1e6 * dt / calls:9.1f} us per call  {calls * n / dt / 1e9:6.3f} G decisions/s", flush=True)
 
 
-for m in modes:
-    run(m)
+for _ in range(int(os.environ.get("ABI_REPEAT", 1))):
+    for m in modes:
+        run(m)
 eng.close()
 
 
