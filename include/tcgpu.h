@@ -623,6 +623,37 @@ int tc_route_inverse(uint32_t world, uint64_t keys_per_shard, uint64_t n, const 
  * the front door of a sharded deployment of key-mode engines: split a key batch by owner, hand every GPU the keys it owns.
  * key_off[n + 1] delimits the keys in key_bytes.  Host only. */
 int tc_route_keys_host(uint32_t world, uint64_t n, const uint8_t* key_bytes, const uint32_t* key_off, uint32_t* owner);
+/* The same split on the device: a key batch that is already in device memory (staged from the host, or handed on by the peer GPU
+ * that took the connection) is partitioned by owner -- the owner map above, bit for bit -- into one arena per destination.
+ * Stable: the keys of a destination keep the order they had in the batch, so a key's requests keep theirs; empty keys are keys.
+ * only == -1: segment d holds count_d keys and bytes_d bytes; with start_d = the counts before d and bstart_d = the bytes before d,
+ *   its bytes are out_bytes + bstart_d, its count_d + 1 offsets are out_off[start_d + d ..] (relative to its own bytes: the first is
+ *   0, the last bytes_d) and the positions its keys had in the batch are out_pos[start_d ..]: (out_bytes + bstart_d,
+ *   out_off + start_d + d, count_d) is a complete arena for tc_rate_limit_batch_keys / tc_throttle_batch_keys (TC_B_DEVICE_PTRS) on
+ *   this GPU, or for a copy to a peer.
+ * only >= 0: that destination's segment alone, at out_bytes, out_off[0 .. count], out_pos[0 .. count).
+ * Nothing beyond that layout is written.  Works on any engine, key mode or not (the key table is not touched); asynchronous on
+ * `stream`.  key_off must not decrease.  Three launches, none of which waits for another workgroup.  A bad world, n, only, flags
+ * or a NULL array: TC_E_INVALID_ARG, nothing is enqueued. */
+typedef struct tc_key_route {
+    uint32_t struct_size;      /* = sizeof(tc_key_route) */
+    uint32_t world;            /* 1..64 */
+    uint64_t n;                /* keys in the batch, 1 .. 2^31 - 1 */
+    const uint8_t* key_bytes;  /* device: the arena */
+    const uint32_t* key_off;   /* device [n + 1] */
+    int32_t only;              /* >= 0: that destination's keys only, from the start of the outputs; -1: every destination's segment */
+    uint32_t flags;            /* must be 0 */
+    uint8_t* out_bytes;        /* device, room for key_off[n] bytes */
+    uint32_t* out_off;         /* device [n + world] */
+    uint32_t* out_pos;         /* device [n] or NULL: position of every kept key in the input batch */
+    uint32_t* out_count;       /* device [2 * world]: keys per destination, then bytes per destination (all of them, whatever `only` is) */
+    void* stream;              /* NULL: the engine's stream.  Else the hipStream_t to enqueue the router on */
+    uint32_t* out_count_host;  /* NULL or PINNED host memory [2 * world + 1] (tc_host_alloc): the same numbers, then `tag`, written last */
+    uint32_t tag;              /* any value the previous use of out_count_host did not leave there */
+    uint32_t reserved;
+} tc_key_route;
+/* r points at a tc_key_route (declared void* for the reason tc_throttle_batch_* give above) */
+int tc_route_keys(tc_engine* e, const void* r);
 
 /* ---- pipeline health --------------------------------------------------------------------------------------------------------
  * Pipelined batches (TC_B_INPUTS_READY, TC_B_ASYNC, pinned host batches in chunks) are fast because their grouping runs on

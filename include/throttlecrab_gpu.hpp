@@ -196,6 +196,12 @@ class GpuStore {
         check(tc_sweep_expired(e_, to_ns(now), &removed));
         return removed;
     }
+    // tc_route_keys: a key batch in DEVICE memory partitioned by owning GPU (every pointer of `r` but out_count_host is a
+    // device pointer; struct_size is filled in here).  Asynchronous on r.stream / the engine's stream.
+    void route_keys(tc_key_route r) {
+        r.struct_size = sizeof r;
+        check(tc_route_keys(e_, &r));
+    }
     tc_engine* handle() { return e_; }
     uint64_t max_batch() const { return max_batch_; }
 

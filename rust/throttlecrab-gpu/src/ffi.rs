@@ -281,6 +281,25 @@ pub struct tc_route {
 }
 
 #[repr(C)]
+pub struct tc_key_route {
+    pub struct_size: u32,
+    pub world: u32,
+    pub n: u64,
+    pub key_bytes: *const u8,
+    pub key_off: *const u32,
+    pub only: i32,
+    pub flags: u32,
+    pub out_bytes: *mut u8,
+    pub out_off: *mut u32,
+    pub out_pos: *mut u32,
+    pub out_count: *mut u32,
+    pub stream: *mut c_void,
+    pub out_count_host: *mut u32,
+    pub tag: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
 pub struct tc_forward {
     pub struct_size: u32,
     pub world: u32,
@@ -367,6 +386,7 @@ extern "C" {
     pub fn tc_exchange_poll(x: *mut tc_exchange) -> c_int;
     pub fn tc_exchange_wait_ns(x: *mut tc_exchange, out: *mut u64) -> c_int;
     pub fn tc_route_keys_host(world: u32, n: u64, key_bytes: *const u8, key_off: *const u32, owner: *mut u32) -> c_int;
+    pub fn tc_route_keys(e: *mut tc_engine, r: *const c_void) -> c_int;
     pub fn tc_route_inverse(world: u32, keys_per_shard: u64, n: u64, owner: *const u32, slot: *const u32, global_id: *mut u64) -> c_int;
     pub fn tc_engine_set_stream(e: *mut tc_engine, hip_stream: *mut c_void) -> c_int;
     pub fn tc_register_params(

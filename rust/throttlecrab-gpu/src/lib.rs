@@ -102,6 +102,17 @@ impl GpuStore {
         if rc == 0 { Ok(removed) } else { Err(call_error(self.e, rc)) }
     }
 
+    /// `tc_route_keys`: a key batch in DEVICE memory partitioned by owning GPU; asynchronous on `r.stream` / the engine's stream.
+    ///
+    /// # Safety
+    /// Every pointer of `r` except `out_count_host` (pinned host memory) must be a device pointer with the room
+    /// `tcgpu.h` asks for, and stay valid until the stream has run the router.
+    pub unsafe fn route_keys(&mut self, mut r: ffi::tc_key_route) -> Result<(), String> {
+        r.struct_size = std::mem::size_of::<ffi::tc_key_route>() as u32;
+        let rc = ffi::tc_route_keys(self.e, &r as *const ffi::tc_key_route as *const std::ffi::c_void);
+        if rc == 0 { Ok(()) } else { Err(call_error(self.e, rc)) }
+    }
+
     pub fn counters(&mut self) -> Result<[u64; ffi::TC_CNT_COUNT], String> {
         let mut out = [0u64; ffi::TC_CNT_COUNT];
         let rc = unsafe { ffi::tc_counters(self.e, out.as_mut_ptr()) };

@@ -68,6 +68,12 @@ class tc_route(C.Structure):
                 ("out_pos", C.c_void_p), ("out_count", C.c_void_p), ("stream", C.c_void_p), ("out_count_host", C.c_void_p), ("tag", C.c_uint32), ("reserved1", C.c_uint32), ("out_dst", C.c_void_p)]
 
 
+class tc_key_route(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("world", C.c_uint32), ("n", C.c_uint64), ("key_bytes", C.c_void_p), ("key_off", C.c_void_p),
+                ("only", C.c_int32), ("flags", C.c_uint32), ("out_bytes", C.c_void_p), ("out_off", C.c_void_p), ("out_pos", C.c_void_p),
+                ("out_count", C.c_void_p), ("stream", C.c_void_p), ("out_count_host", C.c_void_p), ("tag", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class tc_exchange_config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rank", C.c_uint32), ("world", C.c_uint32), ("ring", C.c_uint32), ("seg_cap", C.c_uint32),
                 ("flags", C.c_uint32), ("keys_per_shard", C.c_uint64), ("inbox", C.c_void_p), ("mail", C.c_void_p), ("done", C.c_void_p)]
@@ -175,6 +181,7 @@ SYMBOLS = {
     "tc_route_host": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tc_route_inverse": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tc_route_keys_host": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tc_route_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_key_route)]),
     "tc_slot_keys": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 

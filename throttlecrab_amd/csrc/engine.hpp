@@ -6,7 +6,7 @@
 //   keys.hip      string keys: key stages, tc_rate_limit_batch_keys, tc_rate_limit, the `trait Store` shims
 //   maint.hip     sweep, top denied keys, state introspection
 //   snapshot.hip  tc_snapshot_save / load
-//   route.hip     multi-GPU: tc_route_batch, tc_forward_segments, the host mirror of the map
+//   route.hip     multi-GPU: tc_route_batch, tc_route_keys, tc_forward_segments, the host mirror of the map
 //   autosweep.hip self-cleaning: tc_set_sweep_policy, the policy feed, auto_sweep_before / auto_sweep_after
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,6 +37,7 @@
 #include "bucket_path.hpp"
 #include "maintenance_kernels.hpp"
 #include "route_kernels.hpp"
+#include "key_route.hpp"
 
 using tc::Cell;
 using tc::RateClass;
@@ -336,6 +337,11 @@ struct tc_engine {
     hipEvent_t route_l0_done = nullptr; // the last router that used scratch lane 0 (the caller's stream / the engine's stream) ...
     hipStream_t route_l0_stream = nullptr; // ... and the stream it ran on: a router on ANOTHER stream waits for it (one scratch)
     bool route_l0_used = false;
+    uint8_t* kroute_ws = nullptr;  // tc_route_keys scratch (lazy): two [world][tiles] rows of u32, then the owner column (u8 [n])
+    size_t kroute_ws_bytes = 0;
+    hipEvent_t kroute_done = nullptr;    // the last key router, and the stream it ran on: one on ANOTHER stream waits for it (one scratch)
+    hipStream_t kroute_stream = nullptr;
+    bool kroute_used = false;
 
     // bucket path (bucket_path.hpp): uniform batches are partitioned by key range and ranked per bucket instead of
     // sorted.  Such a batch is enqueued on BOTH paths; the partition's largest bucket (a word in device memory,

@@ -193,3 +193,57 @@ extern "C" int tc_route_keys_host(uint32_t world, uint64_t n, const uint8_t* key
     }
     return TC_E_OK;
 }
+
+// The same split ON THE DEVICE (key_route.hpp): a key batch in HBM -- staged from the host, or handed on by the peer that took the
+// connection -- partitioned by owner into one complete arena per destination.  Works on any engine: the key table is never touched.
+extern "C" int tc_route_keys(tc_engine* e, const void* rp) {
+    if (!e || !rp) return TC_E_INVALID_ARG;
+    tc_key_route r;
+    memcpy(&r, rp, sizeof(uint32_t)); // (struct_size first: nothing beyond it is read from a shorter struct)
+    if (r.struct_size < sizeof(tc_key_route)) return TC_E_INVALID_ARG;
+    memcpy(&r, rp, sizeof r);
+    TC_CHECK_POISON(e);
+    if (r.world == 0 || r.world > krt::MAX_WORLD) return fail(e, TC_E_INVALID_ARG, "tc_route_keys: world must be 1..64");
+    if (r.n == 0 || r.n > 0x7FFFFFFFull) return fail(e, TC_E_INVALID_ARG, "tc_route_keys: n out of range");
+    if (r.only >= (int32_t)r.world || r.only < -1) return fail(e, TC_E_INVALID_ARG, "tc_route_keys: `only` is not a destination");
+    if (r.flags != 0) return fail(e, TC_E_INVALID_ARG, "tc_route_keys: flags must be 0");
+    if (!r.key_bytes || !r.key_off || !r.out_bytes || !r.out_off || !r.out_count) return fail(e, TC_E_INVALID_ARG, "tc_route_keys: NULL array");
+    TC_HIP(e, hipSetDevice(e->device));
+    hipStream_t s = r.stream ? (hipStream_t)r.stream : cur_stream(e);
+    const uint32_t n = (uint32_t)r.n, tiles = (n + krt::TILE - 1) / krt::TILE;
+    // scratch: [ keys per destination and tile: u32 [world][tiles] | their bytes: the same | owner column: u8 [n] ].  Nothing to
+    // clear: k_count writes every word before k_scan reads it.
+    const size_t row_bytes = (size_t)r.world * tiles * sizeof(uint32_t), need = 2 * row_bytes + n;
+    if (need > e->kroute_ws_bytes) {
+        if (e->kroute_ws) {
+            TC_HIP(e, hipDeviceSynchronize()); // (whatever streams earlier routers ran on)
+            (void)hipFree(e->kroute_ws);
+            e->kroute_ws = nullptr;
+            e->kroute_ws_bytes = 0;
+        }
+        const size_t grown = 2 * need; // (room to grow: a reallocation drains the device)
+        TC_HIP(e, hipMalloc(&e->kroute_ws, grown));
+        e->kroute_ws_bytes = grown;
+    }
+    // one scratch: two routers on DIFFERENT streams are ordered by an event instead of racing on it (as tc_route_batch's lane 0)
+    if (!e->kroute_done) TC_HIP(e, hipEventCreateWithFlags(&e->kroute_done, hipEventDisableTiming));
+    if (e->kroute_used && e->kroute_stream != s) TC_HIP(e, hipStreamWaitEvent(s, e->kroute_done, 0));
+    krt::Work w;
+    w.tile_keys = reinterpret_cast<uint32_t*>(e->kroute_ws);
+    w.tile_bytes = reinterpret_cast<uint32_t*>(e->kroute_ws + row_bytes);
+    w.owner = e->kroute_ws + 2 * row_bytes;
+    w.totals = r.out_count;
+    w.tiles = tiles;
+    w.host_totals = r.out_count_host;
+    w.tag = r.tag;
+    hipLaunchKernelGGL(krt::k_count, dim3(tiles), dim3(krt::THREADS), 0, s, r.key_bytes, r.key_off, n, krt::make_mod(r.world), w);
+    hipLaunchKernelGGL(krt::k_scan, dim3(r.world), dim3(krt::THREADS), 0, s, w, r.world);
+    hipLaunchKernelGGL(krt::k_scatter, dim3(tiles), dim3(krt::THREADS), 0, s, r.key_bytes, r.key_off, n, r.world, w, (int)r.only, r.out_bytes,
+                       r.out_off, r.out_pos);
+    if (r.out_count_host) hipLaunchKernelGGL(krt::k_publish, dim3(1), dim3(2 * krt::MAX_WORLD), 0, s, w, r.world);
+    TC_HIP(e, hipGetLastError());
+    TC_HIP(e, hipEventRecord(e->kroute_done, s));
+    e->kroute_stream = s;
+    e->kroute_used = true;
+    return TC_E_OK;
+}

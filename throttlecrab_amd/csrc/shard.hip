@@ -46,7 +46,7 @@ extern "C" int tc_shard_create(tc_engine* e, const tc_shard_config* c, tc_shard*
     if (!rt::make_map(c->world, c->keys_per_shard, &m) || c->rank >= c->world) return fail(e, TC_E_INVALID_ARG, "tc_shard_create: world 1..64, rank < world, keys_per_shard 1..2^32");
     if (c->ring < 2 || c->ring > 64 || c->max_global == 0 || c->max_global > 0x7FFFFFFFull)
         return fail(e, TC_E_INVALID_ARG, "tc_shard_create: ring 2..64 routed batches kept, max_global 1..2^31");
-    if (e->key_mode) return fail(e, TC_E_UNSUPPORTED, "tc_shard_create: slot-mode engines (string keys are sharded by key: tc_route_keys_host)");
+    if (e->key_mode) return fail(e, TC_E_UNSUPPORTED, "tc_shard_create: slot-mode engines (string keys are sharded by key: tc_route_keys on the device, tc_route_keys_host on the host)");
     TC_HIP(e, hipSetDevice(e->device));
     tc_shard* x = new (std::nothrow) tc_shard;
     if (!x) return TC_E_NOMEM;

@@ -500,6 +500,39 @@ class Engine:
         self._check(self._lib.tc_route_batch(self._h, C.byref(r)))
         return slots, pos, counts
 
+    def route_keys(self, key_bytes, key_off, world: int, only: int = -1, want_pos: bool = True, out=None, stream=None,
+                   host_counts=None, tag: int = 0):
+        """tc_route_keys: a string-key arena in device memory (CUDA uint8 bytes, int32 / uint32 offsets[n + 1]) partitioned by
+        owner, stable.  -> (bytes uint8[len(key_bytes)], off int32[n + world], pos int32[n] or None, counts int32[2 * world])
+        CUDA tensors: counts = keys per destination, then bytes per destination.  only = -1: segment d's bytes start at
+        sum(bytes before d), its count + 1 offsets at off[sum(counts before d) + d], its positions at pos[sum(counts before d)];
+        only >= 0: that destination's segment alone, from the start of each tensor.  Asynchronous on the engine's stream (or
+        `stream`, a torch.cuda.Stream): read `counts` after a sync, or hand in host_counts, a pinned uint32 array of
+        2 * world + 1 words (host_alloc) that receives the counts and then `tag` -- poll its last word.
+        `out`: (bytes, off, pos or None, counts) tensors to reuse."""
+        import torch
+        assert key_bytes.is_cuda and key_off.is_cuda and key_bytes.is_contiguous() and key_off.is_contiguous()
+        assert key_bytes.dtype == torch.uint8 and key_off.dtype in (torch.int32, torch.uint32)
+        n = key_off.numel() - 1
+        dev = key_bytes.device
+        if out is None:
+            # (torch.empty: see route_batch)
+            out = (torch.empty(max(1, key_bytes.numel()), dtype=torch.uint8, device=dev), torch.empty(n + world, dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev) if want_pos else None, torch.empty(2 * world, dtype=torch.int32, device=dev))
+        obytes, ooff, pos, counts = out
+        r = L.tc_key_route()
+        r.struct_size = C.sizeof(L.tc_key_route)
+        r.world, r.n, r.only = world, n, only
+        r.key_bytes, r.key_off = key_bytes.data_ptr(), key_off.data_ptr()
+        r.out_bytes, r.out_off, r.out_count = obytes.data_ptr(), ooff.data_ptr(), counts.data_ptr()
+        r.out_pos = pos.data_ptr() if pos is not None else None
+        r.stream = stream.cuda_stream if stream is not None else None
+        if host_counts is not None:
+            assert host_counts.dtype == np.uint32 and host_counts.size >= 2 * world + 1
+            r.out_count_host, r.tag = host_counts.ctypes.data, tag
+        self._check(self._lib.tc_route_keys(self._h, C.byref(r)))
+        return obytes, ooff, pos, counts
+
     def forward_segments(self, src, counts, dsts, stream=None):
         """tc_forward_segments: the router's segments (tc_route_batch with only = -1; `src` = its slot tensor, `counts` = the
         host copy of its counts) -> dsts[d][:counts[d]] for every destination d, in one launch (dsts: CUDA int32 tensors,

@@ -140,6 +140,29 @@ def split_keys(key_bytes: np.ndarray, key_off: np.ndarray, world: int):
     return out
 
 
+def split_keys_device(engine, d_bytes, d_off, n: int, world: int, only: int = -1):
+    """split_keys for an arena that is in device memory (tc_route_keys: CUDA uint8 bytes, int32 offsets[n + 1]), without a host
+    copy of a single key.  -> ([(key_bytes_d, key_off_d, positions_d) for every destination written], counts): views into the
+    router's outputs -- each a complete arena for Engine.rate_limit_batch_keys -- and the host copy of the counts
+    (uint32[2 * world]: keys per destination, then bytes).  only >= 0: one entry, that destination's.  Waits for the router (the
+    views' sizes are its counts)."""
+    host = engine.host_alloc(2 * world + 1, np.uint32)
+    host[2 * world] = 0
+    obytes, ooff, pos, _ = engine.route_keys(d_bytes, d_off[: n + 1], world, only=only, host_counts=host, tag=1)
+    engine.synchronize()
+    assert host[2 * world] == 1
+    counts = host[: 2 * world].copy()
+    if only >= 0:
+        c = int(counts[only])
+        return [(obytes[: int(counts[world + only])], ooff[: c + 1], pos[:c])], counts
+    out, k0, b0 = [], 0, 0
+    for d in range(world):
+        c, b = int(counts[d]), int(counts[world + d])
+        out.append((obytes[b0: b0 + b], ooff[k0 + d: k0 + d + c + 1], pos[k0: k0 + c]))
+        k0, b0 = k0 + c, b0 + b
+    return out, counts
+
+
 # ---- the exchange (see the module docstring) -------------------------------------------------------------------------
 def split_segments(global_slice: np.ndarray, world: int, keys_per_shard: int):
     """Host mirror of tc_route_batch(only = -1): what one source rank sends -- [shard-local slots for destination d,
