@@ -326,6 +326,39 @@ int tc_rate_limit_batch_keys(tc_engine* e, const tc_batch* b);
 int tc_throttle_batch_slots(tc_engine* e, const tc_batch* b, void* out);
 int tc_throttle_batch_keys(tc_engine* e, const tc_batch* b, void* out);
 
+/* ---- read-only batch queries ------------------------------------------------------------------------------------------------
+ * The reference cannot look at a limiter without changing it: a request with quantity 0 stores the clamped TAT and a new TTL on a
+ * known key (rate_limiter.rs:158-195), INSERTS an unknown one (set_if_not_exists_with_ttl) and counts as a store operation.  A
+ * dashboard, a quota display or an admission pre-check over a million string keys would bind a million slots.  These two calls
+ * answer a batch and change nothing.
+ *   Answer i is what rate_limit(key_i, max_burst_i, count_per_period_i, period_i, quantity_i, now_i) would return if it were the
+ *   NEXT AND ONLY request, given the state every earlier call on the engine has left: the reference's arithmetic on a copy of the
+ *   key's entry, the copy thrown away.  An unknown key, an unbound or never-written slot and an entry with expiry <= now_i are
+ *   the reference's "first request" branch (rate_limiter.rs:162-166).  The requests of one peek do not see one another:
+ *   duplicates get identical answers.  Validation and the precedence of the statuses are those of the batch calls; a status other
+ *   than TC_OK gives all-zero values and allowed = 0.
+ *   NOTHING CHANGES: no cell; no key-table entry (nothing claimed, no tombstone recycled, no slot taken, free stack and overflow
+ *   arena as they were); no TC_CNT_* counter (TC_CNT_BATCHES included); no denial counter, no retired key; the cleanup policy's
+ *   operation count does not move and a peek never triggers a sweep; no grouping hint, no hot list.  On a TC_CFG_FIXED_PARAMS
+ *   engine a peek before the first batch does NOT seal the plans -- it decides nothing -- so tc_register_params* still work
+ *   after it.
+ *   Outputs: any of b->decisions (tc_decision[n]), b->allowed, b->status and `out` (tc_throttle[n], 16-byte aligned, or NULL) that
+ *   are given are written, row i for request i; at least one must be.  Any OTHER output pointer of `b` being set: TC_E_INVALID_ARG.
+ *   `out` is declared void* for the reason tc_throttle_batch_* give above.
+ *   Inputs: every form tc_batch has -- scalars or columns; TC_B_PLAN_DICT with quantity32; for slots TC_B_REGISTERED_PARAMS
+ *   (mandatory on a TC_CFG_FIXED_PARAMS engine, as for batches; a slot out of range gets TC_INTERNAL, as there); host pointers
+ *   (pinned or pageable: staged, run, copied back -- the call returns with the answers) or TC_B_DEVICE_PTRS (asynchronous on the
+ *   engine's stream).  n = 1 .. max_batch (n = 0: TC_E_OK, nothing to answer).  TC_B_INPUTS_READY and TC_B_OUTPUTS_IDLE are
+ *   accepted and mean nothing.  TC_B_ASYNC, TC_B_GROUPED_OUTPUT, TC_B_UNIQUE_SLOTS and n_segments > 0: TC_E_UNSUPPORTED.
+ *   tc_peek_batch_keys on an engine without TC_CFG_KEY_MODE: TC_E_UNSUPPORTED.  A refused call enqueues nothing.
+ *   Ordering: a peek sees every batch, sweep and store operation whose call returned before it -- pipelined ones included, whose
+ *   key stages run on a stream of the engine's own -- and nothing of the calls made after it: it is one kernel on the engine's
+ *   stream, behind the last key stage, and the key stage, sweep or table rebuild of a later call does not start before it has
+ *   finished reading.  No host synchronisation is involved for device-pointer peeks.
+ *   Cost: one launch, one lane per request: hash, probe, confirm, one 16-byte cell read, one 16-byte record written. */
+int tc_peek_batch_keys(tc_engine* e, const tc_batch* b, void* out);
+int tc_peek_batch_slots(tc_engine* e, const tc_batch* b, void* out);
+
 /* TC_B_ASYNC batches: block until at most `max_in_flight` of them are still incomplete (0 = all done).
  * A caller that cycles through K sets of pinned buffers calls tc_wait_batches(e, K - 1) before it
  * refills the oldest set.  (The reference's actor answers one request per loop turn,

@@ -11,6 +11,7 @@
 // INTEGRATION.md shows the equivalent Rust `extern "C"` binding.
 #pragma once
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstring>
@@ -272,6 +273,27 @@ class RateLimiter {
         return out;
     }
 
+    // What throttle_batch WOULD answer for each request if it were the next and only one (tc_peek_batch_keys): nothing is applied --
+    // no key inserted, no TAT or TTL stored, no counter or cleanup-policy state moved -- and the requests do not see one another.
+    // The reference has no such call: its quantity-0 request writes (rate_limiter.rs:158-195).
+    std::vector<ThrottleOutcome> peek_batch(const std::vector<Request>& reqs) {
+        std::vector<ThrottleOutcome> out;
+        out.reserve(reqs.size());
+        for (size_t at = 0; at < reqs.size(); at += store_.max_batch()) {
+            const std::vector<Request> chunk(reqs.begin() + at, reqs.begin() + std::min(reqs.size(), at + store_.max_batch()));
+            const size_t n = chunk.size();
+            std::vector<int64_t> burst, qty;
+            std::vector<tc_throttle> thr(n + 1); // (+ 1: room to start at a 16-byte boundary)
+            tc_throttle* t = reinterpret_cast<tc_throttle*>((reinterpret_cast<uintptr_t>(thr.data()) + 15u) & ~uintptr_t(15));
+            const int rc = run_batch(chunk, burst, qty, nullptr, t, true);
+            for (size_t i = 0; i < n; ++i) {
+                if (rc != TC_E_OK) out.push_back(CellError{CellError::Internal, 0, tc_last_error(store_.handle())});
+                else out.push_back(throttle_outcome(t[i], burst[i], qty[i]));
+            }
+        }
+        return out;
+    }
+
     // ---- the same, pipelined -------------------------------------------------------------------
     // submit_batch() marshals the requests into one of FLIGHTS sets of pinned buffers and only enqueues
     // them (TC_B_ASYNC: the PCIe transfers and the evaluation overlap with the caller marshalling the
@@ -389,7 +411,8 @@ class RateLimiter {
     }
 
     // the requests as one synchronous key batch: decisions into `dec`, or (thr != nullptr) throttle records into `thr`
-    int run_batch(const std::vector<Request>& reqs, std::vector<int64_t>& burst, std::vector<int64_t>& qty, tc_decision* dec, tc_throttle* thr) {
+    // peek: asked, not applied (tc_peek_batch_keys)
+    int run_batch(const std::vector<Request>& reqs, std::vector<int64_t>& burst, std::vector<int64_t>& qty, tc_decision* dec, tc_throttle* thr, bool peek = false) {
         const size_t n = reqs.size();
         std::vector<uint8_t> arena;
         std::vector<uint32_t> off(n + 1, 0);
@@ -416,6 +439,7 @@ class RateLimiter {
         b.quantity = qty.data();
         b.now_ns = now.data();
         b.decisions = dec;
+        if (peek) return tc_peek_batch_keys(store_.handle(), &b, thr);
         return thr ? tc_throttle_batch_keys(store_.handle(), &b, thr) : tc_rate_limit_batch_keys(store_.handle(), &b);
     }
 

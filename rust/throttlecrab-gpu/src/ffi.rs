@@ -320,6 +320,8 @@ extern "C" {
     pub fn tc_rate_limit_batch_keys(e: *mut tc_engine, b: *const tc_batch) -> c_int;
     pub fn tc_throttle_batch_slots(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
     pub fn tc_throttle_batch_keys(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
+    pub fn tc_peek_batch_keys(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
+    pub fn tc_peek_batch_slots(e: *mut tc_engine, b: *const tc_batch, out: *mut c_void) -> c_int;
     pub fn tc_wait_batches(e: *mut tc_engine, max_in_flight: u32) -> c_int;
     pub fn tc_host_alloc(bytes: usize) -> *mut c_void;
     pub fn tc_host_free(p: *mut c_void);

@@ -265,8 +265,27 @@ impl GpuRateLimiter {
         let mut out = Vec::with_capacity(reqs.len());
         for chunk in reqs.chunks(self.store.max_batch.max(1)) {
             let n = chunk.len();
-            let rc = self.submit_chunk(chunk, true);
+            let rc = self.submit_chunk(chunk, true, false);
             if rc != 0 && rc != ffi::TC_E_TABLE_FULL {
+                let msg = call_error(self.store.e, rc);
+                out.extend((0..n).map(|_| Err(CellError::Internal(msg.clone()))));
+                continue;
+            }
+            let st = &self.staging;
+            out.extend((0..n).map(|i| unsafe { decode_throttle(&*st.thr.ptr.add(i), *st.burst.ptr.add(i), *st.qty.ptr.add(i)) }));
+        }
+        out
+    }
+
+    /// What `throttle_batch` WOULD answer for each request if it were the next and only one (tc_peek_batch_keys): nothing is
+    /// applied -- no key is inserted, no TAT or TTL stored, no counter or cleanup-policy state moves -- and the requests of the
+    /// slice do not see one another.  The reference has no such call: its quantity-0 request writes (rate_limiter.rs:158-195).
+    pub fn peek_batch(&mut self, reqs: &[Request]) -> Vec<Result<ThrottleOutcome, CellError>> {
+        let mut out = Vec::with_capacity(reqs.len());
+        for chunk in reqs.chunks(self.store.max_batch.max(1)) {
+            let n = chunk.len();
+            let rc = self.submit_chunk(chunk, true, true);
+            if rc != 0 {
                 let msg = call_error(self.store.e, rc);
                 out.extend((0..n).map(|_| Err(CellError::Internal(msg.clone()))));
                 continue;
@@ -282,7 +301,7 @@ impl GpuRateLimiter {
         if n == 0 {
             return;
         }
-        let rc = self.submit_chunk(reqs, false);
+        let rc = self.submit_chunk(reqs, false, false);
         if rc != 0 && rc != ffi::TC_E_TABLE_FULL {
             // nothing was applied: every request of the chunk reports the call's failure
             let msg = call_error(self.store.e, rc);
@@ -296,7 +315,8 @@ impl GpuRateLimiter {
     }
 
     /// marshals a non-empty chunk and runs it: decisions into `staging.dec`, or (throttle) tc_throttle records into `staging.thr`
-    fn submit_chunk(&mut self, reqs: &[Request], throttle: bool) -> i32 {
+    /// peek: tc_peek_batch_keys instead (records into `staging.thr`; nothing is applied)
+    fn submit_chunk(&mut self, reqs: &[Request], throttle: bool, peek: bool) -> i32 {
         let n = reqs.len();
         // The request columns are marshalled straight into PINNED staging (tc_host_alloc) that lives as long as the limiter:
         // the engine's transfers to and from pinned memory run at PCIe speed, and a large batch from pinned arrays is
@@ -384,7 +404,9 @@ impl GpuRateLimiter {
             n_plans: if compact { (st.plans.len() / 3) as u32 } else { 0 },
             reserved_dict: 0,
         };
-        if throttle {
+        if peek {
+            unsafe { ffi::tc_peek_batch_keys(self.store.e, &b, st.thr.ptr as *mut std::os::raw::c_void) }
+        } else if throttle {
             unsafe { ffi::tc_throttle_batch_keys(self.store.e, &b, st.thr.ptr as *mut std::os::raw::c_void) }
         } else {
             unsafe { ffi::tc_rate_limit_batch_keys(self.store.e, &b) }

@@ -129,6 +129,8 @@ SYMBOLS = {
     "tc_rate_limit_batch_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_batch)]),
     "tc_throttle_batch_slots": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
     "tc_throttle_batch_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
+    "tc_peek_batch_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
+    "tc_peek_batch_slots": (C.c_int, [C.c_void_p, C.POINTER(tc_batch), C.c_void_p]),
     "tc_wait_batches": (C.c_int, [C.c_void_p, C.c_uint32]),
     "tc_host_alloc": (C.c_void_p, [C.c_size_t]),
     "tc_host_free": (None, [C.c_void_p]),

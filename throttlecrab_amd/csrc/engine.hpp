@@ -8,6 +8,7 @@
 //   snapshot.hip  tc_snapshot_save / load
 //   route.hip     multi-GPU: tc_route_batch, tc_route_keys, tc_forward_segments, the host mirror of the map
 //   autosweep.hip self-cleaning: tc_set_sweep_policy, the policy feed, auto_sweep_before / auto_sweep_after
+//   peek.hip      read-only batch queries: tc_peek_batch_keys / tc_peek_batch_slots (peek_kernels.hpp, included there alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -457,6 +457,56 @@ class Engine:
                 self._async_keep.append((keep, k2))
         return res
 
+    # ---- read-only queries (tc_peek_batch_*): what rate_limit WOULD answer, nothing changed ----
+    PEEK_FIELDS = ("throttle", "decisions", "allowed", "status")
+
+    def _peek(self, kind, b, res, want, n):
+        bad = [w for w in want if w not in self.PEEK_FIELDS]
+        if bad or not want:
+            raise ValueError(f"a peek writes {self.PEEK_FIELDS} only, not {bad}")
+        t = res.throttle if "throttle" in want else None
+        if n:
+            self._check(getattr(self._lib, "tc_peek_batch_" + kind)(self._h, C.byref(b), None if t is None else (t.data_ptr() if _is_torch(t) else t.ctypes.data)))
+        return res
+
+    def peek_batch_keys(self, key_bytes, key_off, *, max_burst=None, count_per_period=None, period=None, quantity=None,
+                        now_ns=None, want=("throttle",), out: Optional[BatchResult] = None, plan_dict=None) -> BatchResult:
+        """tc_peek_batch_keys: for every string key (arena bytes + offsets[n+1]) what rate_limit would answer if the request were
+        the next and only one -- no key is inserted, no cell, counter or policy state changes, duplicates get identical answers.
+        numpy arrays (host pointers: returns with the answers) or CUDA tensors (asynchronous on the engine's stream), like
+        rate_limit_batch_keys; the same result object (`want` out of PEEK_FIELDS): unpack_throttle / unpack_decisions apply."""
+        dev = _is_torch(key_bytes)
+        if dev:
+            assert key_bytes.is_cuda and key_off.is_cuda
+            keep = [key_bytes, key_off]
+            n = key_off.numel() - 1
+            kb, ko = key_bytes.data_ptr(), key_off.data_ptr()
+        else:
+            kbytes = np.ascontiguousarray(key_bytes, dtype=np.uint8)
+            koff = np.ascontiguousarray(key_off, dtype=np.uint32)
+            keep = [kbytes, koff]
+            n = koff.size - 1
+            kb, ko = kbytes.ctypes.data, koff.ctypes.data
+        b, res, _k2 = self._prepare(n, dev, max_burst, count_per_period, period, quantity, now_ns, False, False, want, out, plan_dict=plan_dict)
+        b.key_bytes, b.key_off = kb, ko
+        return self._peek("keys", b, res, want, n)
+
+    def peek_batch_slots(self, slots, *, max_burst=None, count_per_period=None, period=None, quantity=None, now_ns=None,
+                         registered=False, want=("throttle",), out: Optional[BatchResult] = None, plan_dict=None) -> BatchResult:
+        """tc_peek_batch_slots: the same over pre-resolved slots (registered=True: the slots' registered plans -- mandatory on a
+        fixed_params engine, whose plans a peek does not seal)."""
+        dev = _is_torch(slots)
+        if dev:
+            import torch
+            assert slots.is_cuda and slots.is_contiguous() and slots.dtype in (torch.int32, torch.uint32)
+            sl, n, sp = slots, slots.numel(), slots.data_ptr()
+        else:
+            sl = np.ascontiguousarray(slots, dtype=np.uint32)
+            n, sp = sl.size, sl.ctypes.data
+        b, res, _k2 = self._prepare(n, dev, max_burst, count_per_period, period, quantity, now_ns, registered, False, want, out, plan_dict=plan_dict)
+        b.slot = sp
+        return self._peek("slots", b, res, want, n)
+
     def route_batch(self, global_ids, world: int, only: int = -1, want_pos: bool = False, out=None, stream=None, ahead: bool = False,
                     host_counts=None, tag: int = 0, no_readers: bool = False, out_dst=None):
         """tc_route_batch: of a CUDA tensor of global key ids (int32 / uint32), keep what destination `only` owns
