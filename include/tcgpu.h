@@ -688,6 +688,89 @@ typedef struct tc_key_route {
 /* r points at a tc_key_route (declared void* for the reason tc_throttle_batch_* give above) */
 int tc_route_keys(tc_engine* e, const void* r);
 
+/* ---- live state out of an engine, and into another --------------------------------------------------------------------------
+ * A snapshot moves a whole engine into one of the same capacity and flags.  These two calls move ENTRIES: the live keys of an
+ * engine (or of a page of its slots, or of the share one GPU of a new `world` will own) come out as the project's own arena form
+ * with their TAT and expiry beside them, and such an arena is merged into any other engine -- a larger one (grow), the owner under
+ * a new world (reshard: export with world / only, or export everything and split with tc_route_keys), a standby, or one that
+ * already holds some of the keys (merge).  Device pointers throughout.
+ * Engines: key-mode engines export and import keys, TAT and expiry; slot-mode engines (16-byte cells) the slot instead of the key.
+ * TC_CFG_FIXED_PARAMS engines are OUT OF SCOPE: both calls return TC_E_UNSUPPORTED on them.  NOT CARRIED: denial counters
+ * (TC_CFG_TRACK_DENIED) and the retired keys' counts stay where they are, and so do rate plans registered per slot.
+ *
+ * tc_export_live -- read-only, asynchronous on `stream`.  An entry is live iff expiry > now_ns (the reference's strict test,
+ *   adaptive_cleanup.rs:248) and, in key mode, its slot is bound.  Entry k is the k-th live slot of the page, in ASCENDING slot order:
+ *   out_slot[k], out_tat[k], out_expiry[k], and in key mode its key at out_key_bytes[out_key_off[k] .. out_key_off[k + 1]) -- the first
+ *   offset is 0, the one behind the last entry is the byte total, so (out_key_bytes, out_key_off, count) is a complete arena for
+ *   tc_route_keys, tc_rate_limit_batch_keys, tc_peek_batch_keys and tc_import_live.
+ *   world >= 2 (key mode): only the keys whose owner under tc_route_keys_host's map is `only` -- from the hash the table stores, the
+ *   key bytes are not hashed again.  world 0 or 1: every live key, `only` is ignored.
+ *   out_count[0] = live entries of the page (after the owner filter), out_count[1] = their key bytes: always written.  If they exceed
+ *   cap_entries or cap_bytes (or 2^32 - 1 bytes) NOTHING is written to the entry arrays: read the counts, come again with a smaller
+ *   page or more room.  Nothing beyond the layout above is ever written (out_key_off takes cap_entries + 1 words).
+ *   out_count_host: NULL, or three words of PINNED host memory (tc_host_alloc) that receive the two counts and then `tag`, as soon as
+ *   the counts are known -- a caller that polls the tag learns how much room a repeat needs without a stream synchronisation; the
+ *   entry arrays are complete when `stream` gets there.
+ *   NOTHING CHANGES in the engine, as for tc_peek_batch_*: no cell, key-table word, counter, hint or sweep accounting.  Ordering: the
+ *   export sees every call that returned before it and nothing of those after it -- on the engine's stream, behind the last key stage,
+ *   and the key stage, sweep or rebuild of a later call waits for it; on a `stream` of the caller's the engine's stream is ordered
+ *   in front of the export and behind it.  One export at a time is in flight (they share a scratch).
+ *   Three launches, none of which waits for another workgroup.  struct_size too small, flags != 0, a page that is empty or reaches
+ *   past the capacity, world > 64, world >= 2 with only outside [0, world) or on a slot-mode engine, a required array NULL (always
+ *   out_tat, out_expiry, out_count; key mode out_key_bytes and out_key_off; slot mode out_slot): TC_E_INVALID_ARG, nothing is enqueued. */
+typedef struct tc_export {
+    uint32_t struct_size;     /* = sizeof(tc_export) */
+    uint32_t flags;           /* must be 0 (flags to come are named TC_XP_*) */
+    uint64_t first_slot;      /* the page: slots [first_slot, first_slot + n_slots) */
+    uint64_t n_slots;
+    int64_t now_ns;
+    uint32_t world;           /* 0 / 1: every live key; 2..64 (key mode): the keys of destination `only` */
+    int32_t only;
+    uint64_t cap_entries;     /* room in the outputs: entries ... */
+    uint64_t cap_bytes;       /* ... and key bytes */
+    uint32_t* out_slot;       /* [cap_entries] source slot (slot mode: the key; key mode: optional, may be NULL) */
+    uint8_t* out_key_bytes;   /* key mode: [cap_bytes] */
+    uint32_t* out_key_off;    /* key mode: [cap_entries + 1] */
+    int64_t* out_tat;         /* [cap_entries] */
+    uint64_t* out_expiry;     /* [cap_entries] */
+    uint64_t* out_count;      /* device [2] */
+    uint64_t* out_count_host; /* NULL or pinned [3] */
+    uint64_t tag;             /* any value the previous use of out_count_host did not leave there */
+    void* stream;             /* NULL: the engine's stream */
+} tc_export;
+/* x points at a tc_export (declared void* for the reason tc_throttle_batch_* give above) */
+int tc_export_live(tc_engine* e, const void* x);
+
+/* tc_import_live -- merge n entries into the engine, on the engine's stream, ordered like any key work.
+ *   Key mode: the arena is resolved by the insert stage of a key batch, unchanged (unknown keys are bound, duplicates inside the call
+ *   share a slot, TC_CNT_KEYS_INSERTED and TC_CNT_LIVE_SLOTS move as for a batch).  Slot mode: slot[i] names the cell.
+ *   The cell every entry of the call aimed at one slot leaves behind:
+ *       expiry' = max(resident expiry, imported expiries)
+ *       tat'    = max(imported tats, and the resident tat iff the resident expiry != 0)
+ *   -- commutative and associative, so order and duplicates cannot matter; a larger TAT is more quota consumed, so the merged key is
+ *   never more permissive than either source, and it stays resident as long as either would.  Exact for every int64 TAT.
+ *   REJECTED (counted, nothing merged): an entry with expiry == 0 (it means vacant; in key mode its key is bound all the same, a bound
+ *   slot with a vacant cell as a refused first request leaves one, which the next sweep frees), a slot >= capacity, a key that found
+ *   no slot.  out_count[0] = entries merged, out_count[1] = entries rejected.
+ *   Return: slot mode TC_E_OK, asynchronous.  Key mode: the call waits for its merge and reads the table's "full" word: TC_E_TABLE_FULL
+ *   if a key found no slot (or that of an asynchronous batch before it did) -- the entries that fit were merged, as for
+ *   tc_rate_limit_batch_keys.  Import does not run the cleanup policy, is not a batch (TC_CNT_BATCHES, TC_CNT_TOTAL), and leaves denial
+ *   counters alone.  struct_size, flags != 0, n outside 1 .. max_batch, a required array NULL (always tat, expiry, out_count; key mode
+ *   key_bytes and key_off; slot mode slot): TC_E_INVALID_ARG, nothing is enqueued. */
+typedef struct tc_import {
+    uint32_t struct_size;      /* = sizeof(tc_import) */
+    uint32_t flags;            /* must be 0 */
+    uint64_t n;                /* 1 .. max_batch */
+    const uint32_t* slot;      /* slot mode: [n] */
+    const uint8_t* key_bytes;  /* key mode: the arena ... */
+    const uint32_t* key_off;   /* ... [n + 1] */
+    const int64_t* tat;        /* [n] */
+    const uint64_t* expiry;    /* [n] */
+    uint64_t* out_count;       /* device [2] */
+} tc_import;
+/* m points at a tc_import */
+int tc_import_live(tc_engine* e, const void* m);
+
 /* ---- pipeline health --------------------------------------------------------------------------------------------------------
  * Pipelined batches (TC_B_INPUTS_READY, TC_B_ASYNC, pinned host batches in chunks) are fast because their grouping runs on
  * internal streams BESIDE the evaluation of earlier batches.  Which hardware queue and dispatch pipe a stream lands on depends on

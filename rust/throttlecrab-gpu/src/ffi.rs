@@ -300,6 +300,41 @@ pub struct tc_key_route {
 }
 
 #[repr(C)]
+pub struct tc_export {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub first_slot: u64,
+    pub n_slots: u64,
+    pub now_ns: i64,
+    pub world: u32,
+    pub only: i32,
+    pub cap_entries: u64,
+    pub cap_bytes: u64,
+    pub out_slot: *mut u32,
+    pub out_key_bytes: *mut u8,
+    pub out_key_off: *mut u32,
+    pub out_tat: *mut i64,
+    pub out_expiry: *mut u64,
+    pub out_count: *mut u64,
+    pub out_count_host: *mut u64,
+    pub tag: u64,
+    pub stream: *mut c_void,
+}
+
+#[repr(C)]
+pub struct tc_import {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub n: u64,
+    pub slot: *const u32,
+    pub key_bytes: *const u8,
+    pub key_off: *const u32,
+    pub tat: *const i64,
+    pub expiry: *const u64,
+    pub out_count: *mut u64,
+}
+
+#[repr(C)]
 pub struct tc_forward {
     pub struct_size: u32,
     pub world: u32,
@@ -389,6 +424,8 @@ extern "C" {
     pub fn tc_exchange_wait_ns(x: *mut tc_exchange, out: *mut u64) -> c_int;
     pub fn tc_route_keys_host(world: u32, n: u64, key_bytes: *const u8, key_off: *const u32, owner: *mut u32) -> c_int;
     pub fn tc_route_keys(e: *mut tc_engine, r: *const c_void) -> c_int;
+    pub fn tc_export_live(e: *mut tc_engine, x: *const c_void) -> c_int;
+    pub fn tc_import_live(e: *mut tc_engine, m: *const c_void) -> c_int;
     pub fn tc_route_inverse(world: u32, keys_per_shard: u64, n: u64, owner: *const u32, slot: *const u32, global_id: *mut u64) -> c_int;
     pub fn tc_engine_set_stream(e: *mut tc_engine, hip_stream: *mut c_void) -> c_int;
     pub fn tc_register_params(

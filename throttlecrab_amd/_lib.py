@@ -74,6 +74,18 @@ class tc_key_route(C.Structure):
                 ("out_count", C.c_void_p), ("stream", C.c_void_p), ("out_count_host", C.c_void_p), ("tag", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class tc_export(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("first_slot", C.c_uint64), ("n_slots", C.c_uint64), ("now_ns", C.c_int64),
+                ("world", C.c_uint32), ("only", C.c_int32), ("cap_entries", C.c_uint64), ("cap_bytes", C.c_uint64), ("out_slot", C.c_void_p),
+                ("out_key_bytes", C.c_void_p), ("out_key_off", C.c_void_p), ("out_tat", C.c_void_p), ("out_expiry", C.c_void_p),
+                ("out_count", C.c_void_p), ("out_count_host", C.c_void_p), ("tag", C.c_uint64), ("stream", C.c_void_p)]
+
+
+class tc_import(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n", C.c_uint64), ("slot", C.c_void_p), ("key_bytes", C.c_void_p),
+                ("key_off", C.c_void_p), ("tat", C.c_void_p), ("expiry", C.c_void_p), ("out_count", C.c_void_p)]
+
+
 class tc_exchange_config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rank", C.c_uint32), ("world", C.c_uint32), ("ring", C.c_uint32), ("seg_cap", C.c_uint32),
                 ("flags", C.c_uint32), ("keys_per_shard", C.c_uint64), ("inbox", C.c_void_p), ("mail", C.c_void_p), ("done", C.c_void_p)]
@@ -184,6 +196,8 @@ SYMBOLS = {
     "tc_route_inverse": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tc_route_keys_host": (C.c_int, [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tc_route_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_key_route)]),
+    "tc_export_live": (C.c_int, [C.c_void_p, C.POINTER(tc_export)]),
+    "tc_import_live": (C.c_int, [C.c_void_p, C.POINTER(tc_import)]),
     "tc_slot_keys": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 

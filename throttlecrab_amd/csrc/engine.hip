@@ -634,7 +634,7 @@ extern "C" void tc_engine_destroy(tc_engine* e) {
         for (void* p : sp)
             if (p) (void)hipFree(p);
     }
-    void* ptrs[] = {e->route_ws, e->kroute_ws, e->bp_park, e->cells, e->tat8, e->rate_id, e->classes, e->denied, e->topk_ws, e->probe_ws, e->probe_stamps, e->counters, e->pend, e->chain, e->loaded, e->pend_count,
+    void* ptrs[] = {e->route_ws, e->kroute_ws, e->export_ws, e->bp_park, e->cells, e->tat8, e->rate_id, e->classes, e->denied, e->topk_ws, e->probe_ws, e->probe_stamps, e->counters, e->pend, e->chain, e->loaded, e->pend_count,
                     e->allowed_tmp, e->stage.slot, e->stage.in[0], e->stage.in[1], e->stage.in[2],
                     e->stage.in[3], e->stage.in[4], e->stage.allowed, e->stage.bits, e->stage.out[0],
                     e->stage.out[1], e->stage.out[2], e->stage.out[3], e->stage.status, e->stage.result4, e->stage.decisions, e->stage.order,
@@ -652,6 +652,7 @@ extern "C" void tc_engine_destroy(tc_engine* e) {
     if (e->hot.done) (void)hipFree(e->hot.done);
     if (e->route_l0_done) (void)hipEventDestroy(e->route_l0_done);
     if (e->kroute_done) (void)hipEventDestroy(e->kroute_done);
+    if (e->export_fence) (void)hipEventDestroy(e->export_fence);
     for (uint32_t k = 0; k < e->debug_fillers; ++k) {
         (void)hipStreamSynchronize(e->debug_filler[k]);
         (void)hipStreamDestroy(e->debug_filler[k]);

@@ -9,6 +9,7 @@
 //   route.hip     multi-GPU: tc_route_batch, tc_route_keys, tc_forward_segments, the host mirror of the map
 //   autosweep.hip self-cleaning: tc_set_sweep_policy, the policy feed, auto_sweep_before / auto_sweep_after
 //   peek.hip      read-only batch queries: tc_peek_batch_keys / tc_peek_batch_slots (peek_kernels.hpp, included there alone)
+//   export.hip    live state out of an engine and into another: tc_export_live / tc_import_live (export_kernels.hpp, included there alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -343,6 +344,9 @@ struct tc_engine {
     hipEvent_t kroute_done = nullptr;    // the last key router, and the stream it ran on: one on ANOTHER stream waits for it (one scratch)
     hipStream_t kroute_stream = nullptr;
     bool kroute_used = false;
+    uint8_t* export_ws = nullptr;        // tc_export_live scratch (lazy): bytes per tile (u64), entries per tile (u32), the "it fits" word
+    size_t export_ws_bytes = 0;
+    hipEvent_t export_fence = nullptr;   // an export on a stream of the caller's: the engine's stream before it, and behind it
 
     // bucket path (bucket_path.hpp): uniform batches are partitioned by key range and ranked per bucket instead of
     // sorted.  Such a batch is enqueued on BOTH paths; the partition's largest bucket (a word in device memory,

@@ -583,6 +583,66 @@ class Engine:
         self._check(self._lib.tc_route_keys(self._h, C.byref(r)))
         return obytes, ooff, pos, counts
 
+    # ---- live state out of an engine and into another (tc_export_live / tc_import_live) ----
+    @staticmethod
+    def _ptr(x):
+        """a CUDA tensor's (or pinned numpy array's) address, a raw pointer as it is, None -> NULL"""
+        if x is None or isinstance(x, int):
+            return x
+        return x.data_ptr() if _is_torch(x) else x.ctypes.data
+
+    def export_buffers(self, cap_entries: int, cap_bytes: int = 0) -> dict:
+        """Outputs for export_live with room for cap_entries entries and cap_bytes key bytes: CUDA tensors slot int32[cap_entries],
+        tat / expiry int64[cap_entries], count int64[2] and, on a key-mode engine, key_bytes uint8[cap_bytes], key_off
+        int32[cap_entries + 1] (torch.empty: see route_batch)."""
+        import torch
+        dev = f"cuda:{self.device}"
+        out = {"slot": torch.empty(max(1, cap_entries), dtype=torch.int32, device=dev), "tat": torch.empty(max(1, cap_entries), dtype=torch.int64, device=dev),
+               "expiry": torch.empty(max(1, cap_entries), dtype=torch.int64, device=dev), "count": torch.empty(2, dtype=torch.int64, device=dev),
+               "cap_entries": cap_entries, "cap_bytes": cap_bytes}
+        if self.key_mode:
+            out["key_bytes"] = torch.empty(max(1, cap_bytes), dtype=torch.uint8, device=dev)
+            out["key_off"] = torch.empty(cap_entries + 1, dtype=torch.int32, device=dev)
+        return out
+
+    def export_live(self, out: dict, now_ns: int, first_slot: int = 0, n_slots: Optional[int] = None, world: int = 0, only: int = 0, stream=None,
+                    host_counts=None, tag: int = 0) -> dict:
+        """tc_export_live: the live entries (expiry > now_ns; key mode: bound, and with world >= 2 owned by `only`) of slots
+        [first_slot, first_slot + n_slots) in ascending slot order into `out` (export_buffers, or a dict of CUDA tensors / raw
+        device pointers under the same names; "slot" is optional in key mode).  out["count"] = (entries, key bytes): if they exceed
+        cap_entries / cap_bytes nothing else was written -- read them after a sync and come again.  Read-only, asynchronous on the
+        engine's stream or `stream` (a torch.cuda.Stream).  host_counts: pinned uint64[3] (host_alloc) that gets the counts, then `tag`."""
+        x = L.tc_export()
+        x.struct_size = C.sizeof(L.tc_export)
+        x.first_slot, x.n_slots = first_slot, (self.capacity - first_slot if n_slots is None else n_slots)
+        x.now_ns, x.world, x.only = now_ns, world, only
+        x.cap_entries, x.cap_bytes = out["cap_entries"], out["cap_bytes"]
+        x.out_slot, x.out_tat, x.out_expiry, x.out_count = (self._ptr(out.get(k)) for k in ("slot", "tat", "expiry", "count"))
+        x.out_key_bytes, x.out_key_off = self._ptr(out.get("key_bytes")), self._ptr(out.get("key_off"))
+        x.stream = stream.cuda_stream if stream is not None else None
+        if host_counts is not None:
+            assert host_counts.dtype == np.uint64 and host_counts.size >= 3
+            x.out_count_host, x.tag = host_counts.ctypes.data, tag
+        self._check(self._lib.tc_export_live(self._h, C.byref(x)))
+        return out
+
+    def import_live(self, n: int, tat, expiry, slot=None, key_bytes=None, key_off=None, out_count=None):
+        """tc_import_live: merge n entries (CUDA tensors or raw device pointers: tat int64[n], expiry int64 / uint64[n], and slot
+        int32[n] on a slot-mode engine, the arena key_bytes + key_off int32[n + 1] on a key-mode one) into the engine:
+        expiry' = max(resident, imported), tat' = max(imported, resident iff its expiry != 0).  -> out_count, a CUDA int64[2]
+        tensor: entries merged, entries rejected (expiry == 0, slot out of range, no slot left).  Key mode: returns when merged,
+        TcError TC_E_TABLE_FULL if a key found no slot (the others were merged)."""
+        if out_count is None:
+            import torch
+            out_count = torch.empty(2, dtype=torch.int64, device=f"cuda:{self.device}")
+        m = L.tc_import()
+        m.struct_size = C.sizeof(L.tc_import)
+        m.n = n
+        m.slot, m.key_bytes, m.key_off = self._ptr(slot), self._ptr(key_bytes), self._ptr(key_off)
+        m.tat, m.expiry, m.out_count = self._ptr(tat), self._ptr(expiry), self._ptr(out_count)
+        self._check(self._lib.tc_import_live(self._h, C.byref(m)))
+        return out_count
+
     def forward_segments(self, src, counts, dsts, stream=None):
         """tc_forward_segments: the router's segments (tc_route_batch with only = -1; `src` = its slot tensor, `counts` = the
         host copy of its counts) -> dsts[d][:counts[d]] for every destination d, in one launch (dsts: CUDA int32 tensors,
