@@ -771,6 +771,47 @@ typedef struct tc_import {
 /* m points at a tc_import */
 int tc_import_live(tc_engine* e, const void* m);
 
+/* tc_forget_batch -- remove n named keys (key mode) or slots (slot mode, wide or TC_CFG_FIXED_PARAMS) from the engine, whatever
+ *   their expiry, on the engine's stream, ordered like any key work.  Device pointers throughout.  The reference has no such call: its
+ *   map grows, and an entry leaves when it has expired and a cleanup runs.  Here a key that cannot be removed holds its slot until then.
+ *   AFTER THE CALL every named key or slot behaves as if it had never been seen: the next request for it takes the reference's "first
+ *   request" branch (rate_limiter.rs:162-166), a peek answers as for an unknown key, tc_export_live does not list it, and in key mode
+ *   tc_lookup_slot returns -1.
+ *   Key mode, every distinct key of the call that is bound: what a sweep does to a slot it unbinds -- the cell becomes {0, 0}, the slot
+ *   is unbound and goes back onto the free stack (the next new key may take it), its denial count is retired to the key so that
+ *   tc_top_denied_keys still reports it, the table entry becomes a tombstone (counted: the next sweep decides about a rebuild, as
+ *   today), TC_CNT_LIVE_SLOTS drops by one.  An unknown key is not an error and changes nothing.  The overflow-arena bytes of a long
+ *   key are reclaimed by the next sweep's compaction, as for swept keys.
+ *   Slot mode: the cell becomes vacant ({0, 0}; TC_CFG_FIXED_PARAMS: the vacant TAT).  A slot >= capacity is ignored.  Denial counters
+ *   stay (a slot is the key), and so do the plans registered per slot; on a TC_CFG_FIXED_PARAMS engine the call does not seal the
+ *   plans, because it decides nothing.
+ *   was_live[i] (if given) = 1 iff key or slot i held an entry with expiry > now_ns when the call began (the reference's strict test;
+ *   fixed layout: expiry = TAT + the tolerance of the slot's registered plan), else 0.  Duplicates inside the call get identical
+ *   answers, and the answer never depends on whether a sweep has run, as for peeks.  now_ns is used for nothing else: what is removed
+ *   does not depend on it.
+ *   out_count[0] = distinct entries removed (bound keys unbound, or non-vacant cells vacated), out_count[1] = how many of those were
+ *   live at now_ns.
+ *   NOT MOVED: TC_CNT_SWEPT, TC_CNT_BATCHES, TC_CNT_TOTAL, the cleanup policy's operation count (no sweep is triggered), grouping hints
+ *   and the hot list, rate plans.
+ *   Ordering: asynchronous, no host wait in either mode.  The call sees every call that returned before it (their evaluations are in
+ *   front of it on the engine's stream; it goes behind the key stream's last stage), and the key stage, sweep or rebuild of any later
+ *   call, pipelined ones included, waits for it.  Two launches, neither of which waits for another workgroup.
+ *   struct_size too small, flags != 0, n outside 1 .. max_batch, out_count NULL, key mode with key_bytes or key_off NULL, slot mode
+ *   with slot NULL: TC_E_INVALID_ARG, nothing is enqueued. */
+typedef struct tc_forget {
+    uint32_t struct_size;      /* = sizeof(tc_forget) */
+    uint32_t flags;            /* must be 0 */
+    uint64_t n;                /* 1 .. max_batch */
+    const uint32_t* slot;      /* slot mode: [n] */
+    const uint8_t* key_bytes;  /* key mode: the arena ... */
+    const uint32_t* key_off;   /* ... [n + 1] */
+    int64_t now_ns;            /* only for was_live / out_count[1]; what is removed does not depend on it */
+    uint8_t* was_live;         /* [n] or NULL */
+    uint64_t* out_count;       /* device [2], required */
+} tc_forget;
+/* f points at a tc_forget */
+int tc_forget_batch(tc_engine* e, const void* f);
+
 /* ---- pipeline health --------------------------------------------------------------------------------------------------------
  * Pipelined batches (TC_B_INPUTS_READY, TC_B_ASYNC, pinned host batches in chunks) are fast because their grouping runs on
  * internal streams BESIDE the evaluation of earlier batches.  Which hardware queue and dispatch pipe a stream lands on depends on

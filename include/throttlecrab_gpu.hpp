@@ -203,6 +203,13 @@ class GpuStore {
         r.struct_size = sizeof r;
         check(tc_route_keys(e_, &r));
     }
+    // tc_forget_batch: the keys of an arena in DEVICE memory (keys.key_bytes / key_off / n; was_live and out_count are device
+    // pointers too, out_count is required; struct_size is filled in here) leave the store whatever their expiry, as if they had
+    // never been seen.  Asynchronous on the engine's stream.
+    void forget(tc_forget keys) {
+        keys.struct_size = sizeof keys;
+        check(tc_forget_batch(e_, &keys));
+    }
     tc_engine* handle() { return e_; }
     uint64_t max_batch() const { return max_batch_; }
 

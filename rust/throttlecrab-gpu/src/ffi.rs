@@ -335,6 +335,19 @@ pub struct tc_import {
 }
 
 #[repr(C)]
+pub struct tc_forget {
+    pub struct_size: u32,
+    pub flags: u32,
+    pub n: u64,
+    pub slot: *const u32,
+    pub key_bytes: *const u8,
+    pub key_off: *const u32,
+    pub now_ns: i64,
+    pub was_live: *mut u8,
+    pub out_count: *mut u64,
+}
+
+#[repr(C)]
 pub struct tc_forward {
     pub struct_size: u32,
     pub world: u32,
@@ -426,6 +439,7 @@ extern "C" {
     pub fn tc_route_keys(e: *mut tc_engine, r: *const c_void) -> c_int;
     pub fn tc_export_live(e: *mut tc_engine, x: *const c_void) -> c_int;
     pub fn tc_import_live(e: *mut tc_engine, m: *const c_void) -> c_int;
+    pub fn tc_forget_batch(e: *mut tc_engine, f: *const c_void) -> c_int;
     pub fn tc_route_inverse(world: u32, keys_per_shard: u64, n: u64, owner: *const u32, slot: *const u32, global_id: *mut u64) -> c_int;
     pub fn tc_engine_set_stream(e: *mut tc_engine, hip_stream: *mut c_void) -> c_int;
     pub fn tc_register_params(

@@ -86,6 +86,11 @@ class tc_import(C.Structure):
                 ("key_off", C.c_void_p), ("tat", C.c_void_p), ("expiry", C.c_void_p), ("out_count", C.c_void_p)]
 
 
+class tc_forget(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n", C.c_uint64), ("slot", C.c_void_p), ("key_bytes", C.c_void_p),
+                ("key_off", C.c_void_p), ("now_ns", C.c_int64), ("was_live", C.c_void_p), ("out_count", C.c_void_p)]
+
+
 class tc_exchange_config(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("rank", C.c_uint32), ("world", C.c_uint32), ("ring", C.c_uint32), ("seg_cap", C.c_uint32),
                 ("flags", C.c_uint32), ("keys_per_shard", C.c_uint64), ("inbox", C.c_void_p), ("mail", C.c_void_p), ("done", C.c_void_p)]
@@ -198,7 +203,8 @@ SYMBOLS = {
     "tc_route_keys": (C.c_int, [C.c_void_p, C.POINTER(tc_key_route)]),
     "tc_export_live": (C.c_int, [C.c_void_p, C.POINTER(tc_export)]),
     "tc_import_live": (C.c_int, [C.c_void_p, C.POINTER(tc_import)]),
-    "tc_slot_keys": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "tc_forget_batch": (C.c_int, [C.c_void_p, C.POINTER(tc_forget)]),
+    "tc_slot_keys":(C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

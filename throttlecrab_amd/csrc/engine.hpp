@@ -10,6 +10,7 @@
 //   autosweep.hip self-cleaning: tc_set_sweep_policy, the policy feed, auto_sweep_before / auto_sweep_after
 //   peek.hip      read-only batch queries: tc_peek_batch_keys / tc_peek_batch_slots (peek_kernels.hpp, included there alone)
 //   export.hip    live state out of an engine and into another: tc_export_live / tc_import_live (export_kernels.hpp, included there alone)
+//   forget.hip    named keys / slots out of a live engine: tc_forget_batch (forget_kernels.hpp, included there alone)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -253,6 +253,28 @@ static __global__ __launch_bounds__(BLOCK) void k_touch_mark(const uint32_t* __r
     if (sl < capacity) touched[sl] = (uint8_t)1;
 }
 
+// A bound key loses slot `sl` (k_sweep_fixup below; fk::k_forget_apply, forget_kernels.hpp): cell cleared, unbound, its denials
+// retired to the key (kt::RetiredRec), its table entry a tombstone.  Returns the entry's position: the caller counts the tombstone
+// in that position's shard and puts the slot on the free stack, one lane or one wave at a time.
+__device__ __forceinline__ uint32_t unbind_slot(Cell* __restrict__ cells, const kt::Table& t, uint32_t* __restrict__ denied, uint32_t sl) {
+    Cell z;
+    z.tat = 0;
+    z.expiry = 0;
+    cells[sl] = z;
+    t.bound[sl] = 0;
+    if (denied) {
+        const uint32_t dc = denied[sl];
+        if (dc) {
+            const uint32_t klen = t.rec[sl].len;
+            if (klen != kt::NO_SLOT) kt::retire_denials(t, t.rec[sl].hash, kt::stored_key(t, sl, klen), klen, dc);
+            denied[sl] = 0;
+        }
+    }
+    const uint32_t pos = t.pos_col[sl];
+    *reinterpret_cast<uint32_t*>(&t.ktab[pos].w) = kt::VAL_TOMB; // (little-endian: the `val` half)
+    return pos;
+}
+
 // ... and, once the newest evaluation is done, the marked slots: the mark column is read sixteen slots per lane (most words are zero),
 // every marked slot's cell is requested, the marks are taken off.  A cell still expired at `now` -- the request was an error, or was
 // denied on a key that had expired, or the caller sweeps at a later time than the batch's -- and the key loses its slot exactly as in
@@ -285,21 +307,7 @@ static __global__ __launch_bounds__(BLOCK) void k_sweep_fixup(Cell* __restrict__
             const uint32_t sl = (uint32_t)(v * 16u) + (uint32_t)j;
             if (ex[j] != 0) removed++; // the reference's map only ever held written entries
             unbound++;
-            Cell z;
-            z.tat = 0;
-            z.expiry = 0;
-            cells[sl] = z;
-            t.bound[sl] = 0;
-            if (denied) {
-                const uint32_t dc = denied[sl];
-                if (dc) {
-                    const uint32_t klen = t.rec[sl].len;
-                    if (klen != kt::NO_SLOT) kt::retire_denials(t, t.rec[sl].hash, kt::stored_key(t, sl, klen), klen, dc);
-                    denied[sl] = 0;
-                }
-            }
-            const uint32_t pos = t.pos_col[sl];
-            *reinterpret_cast<uint32_t*>(&t.ktab[pos].w) = kt::VAL_TOMB; // (little-endian: the `val` half)
+            const uint32_t pos = unbind_slot(cells, t, denied, sl);
             atomicAdd(&t.tombs[pos % kt::TOMB_SHARDS], 1u);
             const int at = atomicAdd(t.free_top, 1);
             t.free_slots[at] = sl;

@@ -643,6 +643,43 @@ class Engine:
         self._check(self._lib.tc_import_live(self._h, C.byref(m)))
         return out_count
 
+    def forget_batch(self, n: int, now_ns: int, slot=None, key_bytes=None, key_off=None, was_live=None, out_count=None):
+        """tc_forget_batch: the n named slots (slot int32[n], slot-mode engines) or keys (the arena key_bytes + key_off int32[n + 1],
+        key-mode engines) leave the engine whatever their expiry, as if they had never been seen: cells vacant, and in key mode the
+        slots unbound and free again, the denials retired to their keys.  Unknown keys and slots >= capacity are ignored.
+        was_live: True (or a CUDA uint8[n] tensor to reuse) asks for 1 where the entry's expiry was > now_ns when the call began.
+        -> (out_count, was_live or None); out_count = distinct entries removed, how many of them were live at now_ns.
+        CUDA tensors or raw device pointers: asynchronous on the engine's stream, the results are CUDA tensors (int64[2], uint8[n]).
+        numpy arrays: copied to the device first, the call waits, the results are numpy arrays."""
+        import torch
+        dev = f"cuda:{self.device}"
+        host = any(isinstance(x, np.ndarray) for x in (slot, key_bytes, key_off))
+        if host:  # staged through torch, whose stream is not the engine's: the copies are waited for before the engine reads them
+            def up(x, dt):
+                if not isinstance(x, np.ndarray):
+                    return x
+                a = np.ascontiguousarray(x) if x.size else np.zeros(1, dt)  # (an arena of empty keys still needs an address)
+                same = a.dtype.kind in "iu" and a.dtype.itemsize == np.dtype(dt).itemsize  # uint32 travels as int32: the bits are what counts
+                return torch.from_numpy(a.view(dt) if same else a.astype(dt)).to(dev)
+            slot, key_bytes, key_off = up(slot, np.int32), up(key_bytes, np.uint8), up(key_off, np.int32)
+            torch.cuda.current_stream(self.device).synchronize()
+        if out_count is None:
+            out_count = torch.empty(2, dtype=torch.int64, device=dev)
+        if was_live is True:
+            was_live = torch.empty(n, dtype=torch.uint8, device=dev)
+        elif was_live is False:
+            was_live = None
+        f = L.tc_forget()
+        f.struct_size = C.sizeof(L.tc_forget)
+        f.n, f.now_ns = n, now_ns
+        f.slot, f.key_bytes, f.key_off = self._ptr(slot), self._ptr(key_bytes), self._ptr(key_off)
+        f.was_live, f.out_count = self._ptr(was_live), self._ptr(out_count)
+        self._check(self._lib.tc_forget_batch(self._h, C.byref(f)))
+        if not host:
+            return out_count, was_live
+        self.synchronize()
+        return out_count.cpu().numpy(), (was_live.cpu().numpy() if _is_torch(was_live) else was_live)
+
     def forward_segments(self, src, counts, dsts, stream=None):
         """tc_forward_segments: the router's segments (tc_route_batch with only = -1; `src` = its slot tensor, `counts` = the
         host copy of its counts) -> dsts[d][:counts[d]] for every destination d, in one launch (dsts: CUDA int32 tensors,
